@@ -13,11 +13,20 @@ Usage:
     python bench.py [--gpus N] [--steps K] [--warmup W]          # N > 1: spawns N ranks itself
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
+A plain run does what the headline figure needs: steps 1, 3, 4 and 6 below (its
+warm-up starts with one epoch's full steps, untimed, in place of epoch 0, so a
+short window is timed on a device as warm as a ``--full`` run's).
+``--full`` adds steps 2, 5 and 7 (their fields are null in a plain run's line).
+``--dump-outputs DIR`` writes, after the timed steps, the training state they
+left on rank 0 as DIR/params.npy, DIR/momentum.npy (float32) and DIR/loss.npy
+(float64: summed loss and correct count of the timed steps); the inputs are
+seeded, so two builds run with the same arguments can be compared array by array.
+
 Order of work on every rank (one process per GPU, RCCL process group for N > 1):
 
 1. setup: process group, synthetic data, engine, HIP-graph capture of every step
    graph the run will replay (capture is never inside a timed region);
-2. epoch 0, the reference's own quantity: all 938 steps (incl. the short last
+2. (``--full``) epoch 0, the reference's own quantity: all 938 steps (incl. the short last
    batch) + the 10k-image validation pass.  ``time_elapsed_s`` = the reference's
    span: t0 taken right after ``import torch`` and the package imports (ref
    src/train_dist.py:1-11 imports, :119 t0), to the end of epoch-0 validation
@@ -31,10 +40,10 @@ Order of work on every rank (one process per GPU, RCCL process group for N > 1):
    N > 1, SGD update) from the start of an epoch, bracketed by barrier + device
    synchronisation; the time reported is the max over ranks -> ``value`` =
    whole-job images/s, ``ms_per_step``;
-5. ``epoch_s``: one more full epoch + validation, warm (steady-state epoch time);
+5. (``--full``) ``epoch_s``: one more full epoch + validation, warm (steady-state epoch time);
 6. N > 1: a bitwise replica check of the parameters and momentum over all ranks
    (``replicas_identical``); a run whose replicas differ reports no value;
-7. unless the run itself is fp32 (or ``--no-fp32-record``): the same K-step
+7. (``--full``) unless the run itself is fp32 (or ``--no-fp32-record``): the same K-step
    window and warm epoch again on the exact-fp32 kernels, the reference's own
    precision, as the ``fp32`` sub-record.
 
@@ -91,7 +100,23 @@ def parse(argv=None) -> argparse.Namespace:
                     help="fault-injection test hook: the last rank's exchange pushes go to a dead-end buffer "
                          "(in loopback mode: every virtual peer is dead), so peer waits time out; the bench "
                          "must detect it and re-measure on the process-group all-reduce (config.comm_retry)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: epoch 0 and the reference's span "
+                         "(time_elapsed_s, epoch0_s, epoch0_breakdown), the warm epoch + validation (epoch_s, "
+                         "val_*) and the exact-fp32 sub-record; a plain run sets up, warms up and times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (rank 0's training state after the last "
+                         "timed step) as DIR/<name>.npy: params, momentum (float32), loss (float64)")
     return ap.parse_args(argv)
+
+
+def write_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: one ``<name>.npy`` per array, float32 / float64 as given."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def reduce_max(ctx, values: dict) -> dict:
@@ -161,13 +186,20 @@ def run_cpu(args, ctx, t_start: float, t_proc: float) -> dict:
         tr.train_batch(*next(it))
     barrier(ctx)
     t0 = time.perf_counter()
+    loss = None
     for _ in range(args.steps):
-        tr.train_batch(*next(it))
+        loss = tr.train_batch(*next(it))
     barrier(ctx)
     elapsed = all_reduce_max(ctx, time.perf_counter() - t0)
     now = time.time()
-    same, _, _ = replica_checksum(ctx, torch.cat([p.detach().reshape(-1) for p in tr.model.parameters()]))
-    return {"elapsed": elapsed, "engine": "CPU plumbing (stock PyTorch ops, modular trainer): not a GPU number",
+    flat = torch.cat([p.detach().reshape(-1) for p in tr.model.parameters()])
+    same, _, _ = replica_checksum(ctx, flat)
+    dump = None
+    if args.dump_outputs:
+        dump = {"params": flat.float().cpu().numpy(),
+                "loss": torch.as_tensor([float(loss) if loss is not None else 0.0], dtype=torch.float64).numpy()}
+    return {"elapsed": elapsed, "dump": dump,
+            "engine": "CPU plumbing (stock PyTorch ops, modular trainer): not a GPU number",
             "allreduce": f"process group ({ctx.backend})" if ctx.is_distributed else "none",
             "time_elapsed_s": all_reduce_max(ctx, now - t_start), "process_elapsed_s": all_reduce_max(ctx, now - t_proc),
             "replicas": same}
@@ -415,6 +447,7 @@ def main(argv=None) -> int:
             None, None, 0, None
         process_elapsed, replicas, fp32_rec = r["process_elapsed_s"], r["replicas"], None
         data_src = e0_rec = ew_rec = None
+        dump = r["dump"]
         from csed_514_project_distributed_training_using_pytorch_amd.parallel import ipc as _ipc_cpu
 
         xdiag = _ipc_cpu.gather_diag(ctx, dict(_ipc_cpu.empty_diag(ctx), allreduce=r["allreduce"],
@@ -498,28 +531,30 @@ def main(argv=None) -> int:
 
             new_epoch()
             full = eng.full_steps()
-            t_mark = time.time()
-            if use_graph:  # the graphs epoch 0 replays (the timed K-step graph: after the span)
-                with prof.range("bench:capture"):
-                    eng.prepare(spg, ks=(full,))
-            ph["capture"] = time.time() - t_mark
-            ph.update({k: v for k, v in eng.bringup_s.items() if k.startswith("capture.")})
-            t_mark = time.time()
-            eng._device_data(test)  # test set upload is data loading (ref: DataLoader), not epoch work
-            ph["test_upload"] = time.time() - t_mark
-            # 2. epoch 0, cold: the reference's time_elapsed (process start -> epoch-0 validation),
-            # every launch stamped (HIP events + host clock; --epoch0-stamps keeps the per-replay list)
-            sync_barrier()
-            st0 = EpochStamps(ctx.device)
-            te = time.perf_counter()
-            with prof.range("bench:epoch0"):
-                full_epoch(st0)
-            sync_barrier()
-            ph["epoch0"] = time.perf_counter() - te
-            epoch0 = all_reduce_max(ctx, ph["epoch0"])
-            now = time.time()
-            t_el = all_reduce_max(ctx, now - t_start)  # the reference's span (t0 after the imports)
-            p_el = all_reduce_max(ctx, now - t_proc)  # from process start
+            st0 = epoch0 = t_el = p_el = None
+            if args.full:
+                t_mark = time.time()
+                if use_graph:  # the graphs epoch 0 replays (the timed K-step graph: after the span)
+                    with prof.range("bench:capture"):
+                        eng.prepare(spg, ks=(full,))
+                ph["capture"] = time.time() - t_mark
+                ph.update({k: v for k, v in eng.bringup_s.items() if k.startswith("capture.")})
+                t_mark = time.time()
+                eng._device_data(test)  # test set upload is data loading (ref: DataLoader), not epoch work
+                ph["test_upload"] = time.time() - t_mark
+                # 2. epoch 0, cold: the reference's time_elapsed (process start -> epoch-0 validation),
+                # every launch stamped (HIP events + host clock; --epoch0-stamps keeps the per-replay list)
+                sync_barrier()
+                st0 = EpochStamps(ctx.device)
+                te = time.perf_counter()
+                with prof.range("bench:epoch0"):
+                    full_epoch(st0)
+                sync_barrier()
+                ph["epoch0"] = time.perf_counter() - te
+                epoch0 = all_reduce_max(ctx, ph["epoch0"])
+                now = time.time()
+                t_el = all_reduce_max(ctx, now - t_start)  # the reference's span (t0 after the imports)
+                p_el = all_reduce_max(ctx, now - t_proc)  # from process start
             # a path timing deferred by the lazy-RCCL bring-up (fused exchange vs RCCL all-reduce;
             # collective, creates the RCCL communicator): outside the span, before anything timed
             t_mark = time.time()
@@ -533,9 +568,18 @@ def main(argv=None) -> int:
             ph["path_select"] = time.time() - t_mark
             if use_graph:  # the timed window's graphs (outside the span: not epoch-0 work)
                 t_mark = time.time()
-                eng.prepare(spg, ks=(full, *epoch_chunks(args.steps, 0, full)) if switched
-                            else tuple(epoch_chunks(args.steps, 0, full)), tail=switched)
+                recapture = switched and args.full  # (the warm epoch's graphs were dropped with the path)
+                eng.prepare(spg, ks=(full, *epoch_chunks(args.steps, 0, full)) if recapture
+                            else tuple(epoch_chunks(args.steps, 0, full)), tail=recapture)
                 ph["capture_timed"] = time.time() - t_mark
+            if not args.full:
+                # a plain run has no epoch 0 in front of its window: one epoch's full steps, untimed
+                # (~13 ms at global batch 64), bring the device to the state a --full run times in.
+                # Measured on one box, 6 alternations of --steps 20 --warmup 5: 14.55 us/step without
+                # them, 14.06 with, 14.09 after a real epoch 0 (at --steps 500 all three read 13.2)
+                new_epoch()
+                advance(full)
+                sync_barrier()
             # 3. warm-up, then a rehearsal of the timed sequence (same graphs, same order)
             with prof.range("bench:warmup"):
                 new_epoch()
@@ -563,10 +607,17 @@ def main(argv=None) -> int:
                 t1 = time.perf_counter()
             elapsed = all_reduce_max(ctx, t1 - t0)
             dev_ms = all_reduce_max(ctx, ev.ms())
-            loss_sum, _ = eng.take_loss()
-            # 5. one more full epoch + validation, warm (order prepared before the clock starts)
+            loss_sum, correct = eng.take_loss()
+            dump = None
+            if args.dump_outputs:  # the training state the K timed steps left, and their loss sums
+                import numpy as np
+
+                dump = {"params": eng.flat.data.detach().float().cpu().numpy(),
+                        "momentum": eng.momentum_buf.detach().float().cpu().numpy(),
+                        "loss": np.array([loss_sum, correct], dtype=np.float64)}
+            # 5. (--full) one more full epoch + validation, warm (order prepared before the clock starts)
             epoch_s = val = stw = None
-            if not args.no_epoch:
+            if args.full and not args.no_epoch:
                 sampler.set_epoch(state["epoch"])
                 order = sampler.indices()
                 new_epoch(order)
@@ -585,9 +636,10 @@ def main(argv=None) -> int:
             same_p, _, _ = replica_checksum(ctx, eng.flat.data)
             same_m, _, _ = replica_checksum(ctx, eng.momentum_buf)
             return dict(eng=eng, elapsed=elapsed, dev_ms=dev_ms, loss_sum=loss_sum, epoch0=epoch0, t_el=t_el,
-                        p_el=p_el,
+                        p_el=p_el, dump=dump,
                         epoch_s=epoch_s, val=val, err=err, replicas=same_p and same_m,
-                        e0=st0.summary(args.epoch0_stamps), ew=stw.summary(args.epoch0_stamps) if stw else None,
+                        e0=st0.summary(args.epoch0_stamps) if st0 else None,
+                        ew=stw.summary(args.epoch0_stamps) if stw else None,
                         xdiag=eng.exchange_diag(),
                         diag=eng.comm_diag() if err else None)
 
@@ -623,7 +675,7 @@ def main(argv=None) -> int:
         if first_fault is not None:
             first_fault["exchange_diag_first_run"] = first_fault_diag
         elapsed, time_elapsed, epoch0_s, epoch_s, val = r["elapsed"], r["t_el"], r["epoch0"], r["epoch_s"], r["val"]
-        process_elapsed = r["p_el"]
+        process_elapsed, dump = r["p_el"], r["dump"]
         comm_err, replicas = r["err"], r["replicas"]
         loss_avg = r["loss_sum"] / max(1, args.steps * eng.B)
         engine_kernels = {"fused-ipc": " with in-kernel xGMI gradient exchange", "none": ""}.get(
@@ -650,9 +702,9 @@ def main(argv=None) -> int:
             extra["allreduce_note"] = _ipc.LAST_NOTE
         if first_fault:
             extra["first_run_fault"] = first_fault
-        # 7. the reference's precision (src/model.py: fp32 defaults) on the same window + warm epoch
+        # 7. (--full) the reference's precision (src/model.py: fp32 defaults) on the same window + warm epoch
         fp32_rec = None
-        if args.dtype != "fp32" and not args.no_fp32_record and not args.inject_exchange_fault:
+        if args.full and args.dtype != "fp32" and not args.no_fp32_record and not args.inject_exchange_fault:
             sync_barrier()
             donor = eng if eng.exch is not None and not eng.loopback_world else None
             if donor is None:
@@ -749,6 +801,9 @@ def main(argv=None) -> int:
                 fp32_rec["vs_baseline_epoch"] = round(base / fp32_rec["epoch_s"], 1)
         if val:
             rec.update({k: round(v, 4) for k, v in val.items()})
+        if args.dump_outputs and dump:
+            write_outputs(args.dump_outputs, dump)
+            rec["outputs"] = {k: list(v.shape) for k, v in dump.items()}
         print(json.dumps(rec), flush=True)
     if ctx.is_distributed:
         dist.destroy_process_group()

@@ -38,6 +38,31 @@ def test_bringup_starts_no_job_work_before_t0(monkeypatch):
     assert names[0] == "t0" and set(names[1:]) == {"native_data", "hip_ctx_thread"}
 
 
+def test_bench_dump_outputs_repeatable_cpu(tmp_path):
+    """--dump-outputs writes float32 / float64 .npy arrays of what the timed steps computed, and
+    two runs with the same arguments see the same inputs: the arrays are equal.  --full is
+    accepted (the CPU plumbing run has nothing behind it)."""
+    import numpy as np
+
+    outs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, "bench.py", "--device", "cpu", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d), *extra], cwd=ROOT, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["loss.npy", "params.npy"] and set(rec["outputs"]) == {"loss", "params"}
+        outs.append({p.stem: np.load(p) for p in d.iterdir()})
+    for o in outs:
+        assert o["params"].dtype == np.float32 and o["params"].shape == (21840,)
+        assert o["loss"].dtype == np.float64 and np.isfinite(o["loss"]).all()
+    assert np.array_equal(outs[0]["params"], outs[1]["params"])
+    assert np.array_equal(outs[0]["loss"], outs[1]["loss"])
+
+
 def test_bench_json_reports_both_spans_cpu():
     r = subprocess.run([sys.executable, "bench.py", "--device", "cpu", "--steps", "2", "--warmup", "1"], cwd=ROOT,
                        capture_output=True, text=True, timeout=300)

@@ -99,6 +99,51 @@ def test_bench_contract_json():
     assert abs(rec["value"] - 64 / (rec["ms_per_step"] * 1e-3)) / rec["value"] < 0.01
 
 
+def test_bench_plain_run_dumps_outputs_and_skips_full_parts(tmp_path):
+    """A plain run times the steps only (the --full fields are null) and --dump-outputs writes the
+    training state the timed steps left: float32 params / momentum, float64 loss sums."""
+    import json
+
+    import numpy as np
+
+    r = _run(["bench.py", "--gpus", "1", "--steps", "24", "--warmup", "4", "--steps-per-graph", "8",
+              "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 24 and rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["dtype"] == "bf16"
+    for k in ("time_elapsed_s", "epoch0_s", "epoch_s", "epoch0_breakdown", "epoch_breakdown"):
+        assert rec[k] is None, (k, rec[k])
+    assert "fp32" not in rec and "val_acc" not in rec
+    out = {p.stem: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert set(out) == {"params", "momentum", "loss"}
+    assert out["params"].dtype == np.float32 and out["params"].shape == (21840,)
+    assert out["momentum"].dtype == np.float32 and out["momentum"].shape == (21840,)
+    assert out["loss"].dtype == np.float64 and out["loss"].shape == (2,)
+    assert np.isfinite(out["params"]).all() and np.isfinite(out["momentum"]).all()
+    assert np.abs(out["momentum"]).max() > 0  # the steps ran
+    # the loss sums cover exactly the 24 timed steps of 64 samples: the line's mean loss (4 decimals),
+    # below a uniform guess's ln(10) after the warm-up's training
+    assert 0 <= out["loss"][1] <= 24 * 64
+    assert abs(out["loss"][0] / (24 * 64) - rec["train_loss_timed_rank0"]) < 1e-4
+    assert 0 < out["loss"][0] / (24 * 64) < 2.3026
+
+
+def test_bench_full_run_reports_epochs_and_fp32():
+    """--full keeps what a plain run leaves out: epoch 0 and the reference's span, the warm epoch
+    with its validation, and the exact-fp32 sub-record."""
+    import json
+
+    r = _run(["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads([l for l in r.stdout.splitlines() if l.strip().startswith("{")][-1])
+    assert rec["value"] > 0 and 0 < rec["time_elapsed_s"] < rec["process_elapsed_s"]
+    assert rec["epoch0_s"] > 0 and rec["epoch_s"] > 0 and 0 <= rec["val_acc"] <= 1
+    assert rec["epoch0_breakdown"]["replays"] > 0 and rec["epoch_breakdown"]["replays"] > 0
+    assert rec["fp32"]["value"] > 0 and rec["fp32"]["epoch_s"] > 0
+
+
 def test_graft_smoke_entry():
     r = _run(["-c", "import __graft_entry__ as g; g.smoke()"])
     assert r.returncode == 0, r.stderr[-3000:]

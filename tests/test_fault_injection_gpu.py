@@ -149,7 +149,7 @@ def test_bench_two_ranks_lazy_rccl_shared_gpu(tmp_path):
     exchange."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(CSED_IPC_TIMEOUT_S="5")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env, cwd=tmp_path)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -52,20 +52,20 @@ task_suite() {
 }
 
 task_bench() {
-  cd $R && py 200 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${T}_bench_driver.json 2>$O/${T}_bench_driver.err && \
-  py 200 python bench.py > $O/${T}_bench_default.json 2>$O/${T}_bench_default.err && \
-  py 200 python bench.py --dtype fp32 > $O/${T}_bench_fp32.json 2>$O/${T}_bench_fp32.err && \
-  py 200 python bench.py --global-batch 8 --steps 3000 --warmup 300 --no-epoch > $O/${T}_bench_b8.json 2>$O/${T}_bench_b8.err && \
-  py 200 python bench.py --global-batch 8 --loopback-world 8 --steps 3000 --warmup 300 --no-epoch > $O/${T}_bench_lb8.json 2>$O/${T}_bench_lb8.err && \
-  py 200 python bench.py --global-batch 1024 --dtype fp16 --steps 300 --warmup 30 --no-epoch > $O/${T}_bench_1024.json 2>$O/${T}_bench_1024.err && \
-  py 200 python bench.py --global-batch 8192 --dtype fp16 --steps 40 --warmup 5 > $O/${T}_bench_8192.json 2>$O/${T}_bench_8192.err
+  cd $R && py 200 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${T}_bench_driver.json 2>$O/${T}_bench_driver.err && \
+  py 200 python bench.py --full > $O/${T}_bench_default.json 2>$O/${T}_bench_default.err && \
+  py 200 python bench.py --dtype fp32 --full > $O/${T}_bench_fp32.json 2>$O/${T}_bench_fp32.err && \
+  py 200 python bench.py --global-batch 8 --steps 3000 --warmup 300 --no-epoch --full > $O/${T}_bench_b8.json 2>$O/${T}_bench_b8.err && \
+  py 200 python bench.py --global-batch 8 --loopback-world 8 --steps 3000 --warmup 300 --no-epoch --full > $O/${T}_bench_lb8.json 2>$O/${T}_bench_lb8.err && \
+  py 200 python bench.py --global-batch 1024 --dtype fp16 --steps 300 --warmup 30 --no-epoch --full > $O/${T}_bench_1024.json 2>$O/${T}_bench_1024.err && \
+  py 200 python bench.py --global-batch 8192 --dtype fp16 --steps 40 --warmup 5 --full > $O/${T}_bench_8192.json 2>$O/${T}_bench_8192.err
 }
 
 task_rehearse() {
-  cd $R && py 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${T}_reh_n1.json 2>$O/${T}_reh_n1.err && \
-  py 300 python bench.py --gpus 2 --backend gloo --steps 20 --warmup 5 > $O/${T}_reh_gloo2.json 2>$O/${T}_reh_gloo2.err && \
-  CSED_TIME_PATHS=1 py 300 python bench.py --gpus 2 --backend gloo --steps 20 --warmup 5 --no-fp32-record > $O/${T}_reh_gloo2_tp.json 2>$O/${T}_reh_gloo2_tp.err && \
-  py 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node=2 --master-addr 127.0.0.1 --master-port 29621 bench.py --gpus 2 --steps 20 --warmup 5 > $O/${T}_reh_nccl2.json 2>$O/${T}_reh_nccl2.err && \
+  cd $R && py 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${T}_reh_n1.json 2>$O/${T}_reh_n1.err && \
+  py 300 python bench.py --gpus 2 --backend gloo --steps 20 --warmup 5 --full > $O/${T}_reh_gloo2.json 2>$O/${T}_reh_gloo2.err && \
+  CSED_TIME_PATHS=1 py 300 python bench.py --gpus 2 --backend gloo --steps 20 --warmup 5 --no-fp32-record --full > $O/${T}_reh_gloo2_tp.json 2>$O/${T}_reh_gloo2_tp.err && \
+  py 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node=2 --master-addr 127.0.0.1 --master-port 29621 bench.py --gpus 2 --steps 20 --warmup 5 --full > $O/${T}_reh_nccl2.json 2>$O/${T}_reh_nccl2.err && \
   for n in 2 4 8; do
     py 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node=$n --master-addr 127.0.0.1 --master-port $((29600 + n)) bench.py --gpus $n --device cpu --steps 2 --warmup 1 > $O/${T}_reh_cpu$n.json 2>$O/${T}_reh_cpu$n.err || return 1
   done && \
@@ -201,18 +201,18 @@ task_ipcmem() {
 }
 
 task_epoch0() {
-  cd $R && py 200 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${T}_e0_driver.json 2>$O/${T}_e0_driver.err && \
-  py 200 python bench.py --gpus 1 --steps 20 --warmup 5 --epoch0-stamps > $O/${T}_e0_stamps.json 2>$O/${T}_e0_stamps.err && \
-  py 200 python bench.py --gpus 1 --steps 20 --warmup 5 --dtype fp32 --epoch0-stamps > $O/${T}_e0_fp32.json 2>$O/${T}_e0_fp32.err && \
-  CSED_PRELOAD=1 py 200 python bench.py --gpus 1 --steps 20 --warmup 5 --epoch0-stamps > $O/${T}_e0_preload.json 2>$O/${T}_e0_preload.err && \
+  cd $R && py 200 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${T}_e0_driver.json 2>$O/${T}_e0_driver.err && \
+  py 200 python bench.py --gpus 1 --steps 20 --warmup 5 --epoch0-stamps --full > $O/${T}_e0_stamps.json 2>$O/${T}_e0_stamps.err && \
+  py 200 python bench.py --gpus 1 --steps 20 --warmup 5 --dtype fp32 --epoch0-stamps --full > $O/${T}_e0_fp32.json 2>$O/${T}_e0_fp32.err && \
+  CSED_PRELOAD=1 py 200 python bench.py --gpus 1 --steps 20 --warmup 5 --epoch0-stamps --full > $O/${T}_e0_preload.json 2>$O/${T}_e0_preload.err && \
   py 120 python tools/firstlaunch_probe.py > $O/${T}_e0_probe.json 2>$O/${T}_e0_probe.err && \
   py 120 python tools/firstlaunch_probe.py --preload > $O/${T}_e0_probe_pre.json 2>$O/${T}_e0_probe_pre.err && \
-  py 200 python bench.py --gpus 1 --steps 20 --warmup 5 --epoch0-stamps > $O/${T}_e0_stamps2.json 2>$O/${T}_e0_stamps2.err
+  py 200 python bench.py --gpus 1 --steps 20 --warmup 5 --epoch0-stamps --full > $O/${T}_e0_stamps2.json 2>$O/${T}_e0_stamps2.err
 }
 
 task_bringtrace() {  # HIP-API + kernel + copy trace of the bench's bring-up (tools/bringup_trace.py)
   cd /tmp && export TMPDIR=/tmp && \
-  py 200 rocprofv3 --hip-trace --kernel-trace --memory-copy-trace --output-format csv -d $O/${T}_bt -o run -- python3 $R/bench.py --steps 20 --warmup 5 --no-fp32-record --no-epoch > $O/${T}_bt.log 2>&1 && \
+  py 200 rocprofv3 --hip-trace --kernel-trace --memory-copy-trace --output-format csv -d $O/${T}_bt -o run -- python3 $R/bench.py --steps 20 --warmup 5 --no-fp32-record --no-epoch --full > $O/${T}_bt.log 2>&1 && \
   cd $R && python3 tools/bringup_trace.py $O/${T}_bt --min-ms 0.3 > $O/${T}_bt_summary.txt 2>&1
 }
 
@@ -222,7 +222,7 @@ task_graphab() {  # native HipGraph vs torch.cuda.CUDAGraph step graphs, alterna
   for i in 1 2 3; do for v in ${GRAPH_AB:-native torch}; do
     case $v in native) E=CSED_NATIVE_GRAPH=1;; nativeflags) E="CSED_NATIVE_GRAPH=1 CSED_GRAPH_FLAGS=1";; nativeupload) E="CSED_NATIVE_GRAPH=1 CSED_GRAPH_UPLOAD=1";;
       stream) E=CSED_BENCH_STREAM=1;; nativestream) E="CSED_NATIVE_GRAPH=1 CSED_BENCH_STREAM=1";; *) E=CSED_NATIVE_GRAPH=0;; esac
-    echo "$v driver $(env $E timeout -k 10 100 python bench.py --gpus 1 --steps 20 --warmup 5 --no-fp32-record 2>/dev/null | python3 -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["ms_per_step"], d["time_elapsed_s"], d["epoch_s"])')" >> $O/${T}_graphab.log || return 1
+    echo "$v driver $(env $E timeout -k 10 100 python bench.py --gpus 1 --steps 20 --warmup 5 --no-fp32-record --full 2>/dev/null | python3 -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["ms_per_step"], d["time_elapsed_s"], d["epoch_s"])')" >> $O/${T}_graphab.log || return 1
     echo "$v long $(env $E timeout -k 10 100 python bench.py --steps 3000 --warmup 300 --no-epoch --no-fp32-record 2>/dev/null | python3 -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["ms_per_step"])')" >> $O/${T}_graphab.log || return 1
   done; done
 }

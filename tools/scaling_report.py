@@ -8,6 +8,8 @@ records into the same quantity side by side:
 
     python tools/scaling_report.py BENCH_or_SCALE_files... [--out profiles/scaling] [--title T]
 
+The records must come from ``bench.py --full``: a plain run leaves ``epoch_s`` and
+``time_elapsed_s`` null.
 Inputs are any mix of files holding bench JSON lines (one record per line, e.g. logs) or JSON
 documents (e.g. the driver's SCALE_rNN.json) in which every dict with "n_gpus" and "value"
 keys counts as a record.  For each N the last record wins.  Outputs ``<out>.md`` (table) and
