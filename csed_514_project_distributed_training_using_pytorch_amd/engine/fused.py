@@ -34,9 +34,12 @@ through the op library, ``state_dict()``) without copies.
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 import sys
+from collections import namedtuple
+from typing import NamedTuple
 
 import torch
 import torch.distributed as dist
@@ -115,41 +118,43 @@ def _hip_graph_upload(exec_handle: int, stream: int) -> bool:
     return fn(ctypes.c_void_p(exec_handle), ctypes.c_void_p(stream)) == 0
 
 
-def layout() -> tuple[int, int, int, int]:
-    """Buffer sizes of the fused kernels, from the extension (csrc/kernels/lenet_fused.hip):
-    16-bit weight-image elements (I_END), conv slab row per workgroup (CNP_PAD: conv1.w/b +
-    conv2.w/b = 5280 floats in 64-float chunks), per-sample fc vector length (VEC) and the
-    largest per-rank batch that uses batch staging (STAGE_MAXB)."""
-    wimg, conv, vec, nparams, stage_max, *_ = (int(v) for v in torch.ops.csed.lenet_layout())
-    assert nparams == N_PARAMS
-    return wimg, conv, vec, stage_max
+class LenetLayout(NamedTuple):
+    """Buffer sizes and batch thresholds of the fused kernels: ``csed::lenet_layout()``'s values, in its order."""
+    wimg_elems: int  # 16-bit weight-image elements (I_END)
+    conv_params: int  # conv slab row per workgroup (CNP_PAD: conv1.w/b + conv2.w/b = 5280 floats in 64-float chunks)
+    vec_len: int  # per-sample fc vector length (VEC)
+    n_params: int  # flat parameters
+    stage_max_batch: int  # largest per-rank batch that uses batch staging (STAGE_MAXB)
+    exch_words: int  # 8-byte words per sender of lenet_update's fused exchange buffer
+    split_k: int  # workgroups per sample of the split step (csed::lenet_train KS)
+    tile_samples: int  # samples per tile of the sample-tile training kernel (csrc/kernels/lenet_tile.hip)
+    tile_min_batch: int  # smallest per-rank batch the auto mode runs on the sample-tile kernel
 
 
-def split_factor() -> int:
-    """Workgroups per sample of the split step (csed::lenet_train KS)."""
-    return int(torch.ops.csed.lenet_layout()[6])
-
-
-def tile_samples() -> int:
-    """Samples per tile of the sample-tile training kernel (csrc/kernels/lenet_tile.hip)."""
+@functools.lru_cache(maxsize=None)
+def lenet_layout() -> LenetLayout:
     _native.require()
-    return int(torch.ops.csed.lenet_layout()[7])
-
-
-def tile_min_batch() -> int:
-    """Smallest per-rank batch the auto mode runs on the sample-tile kernel."""
-    _native.require()
-    return int(torch.ops.csed.lenet_layout()[8])
+    lay = LenetLayout(*(int(v) for v in torch.ops.csed.lenet_layout()))
+    assert lay.n_params == N_PARAMS
+    return lay
 
 
 def tile_grid(B: int) -> int:
     """Workgroups of the sample-tile kernel at per-rank batch B."""
-    return min(256, -(-B // tile_samples()))
+    return min(256, -(-B // lenet_layout().tile_samples))
 
 
-def exch_words() -> int:
-    """8-byte words per sender of lenet_update's fused exchange buffer."""
-    return int(torch.ops.csed.lenet_layout()[5])
+# Argument names of a step's two launches in the order of their op schemas (csrc/bindings.cpp; LenetStepper's
+# set_train / set_update take the same lists): filled in by FusedLeNetTrainer.train_args / update_args alone.
+TRAIN_FIELDS = ("images", "labels", "perm", "cursor", "B", "rank", "wimg", "params", "slab", "vslab", "loss_parts",
+                "grad_scale", "mean", "std", "drop_p", "seed", "rng_offset", "grid", "mfma_dtype", "dbg", "xstage",
+                "lstage", "stage_next", "kernel")
+UPDATE_FIELDS = ("slab", "grid", "vslab", "B", "grad_in", "grad_out", "params", "momentum", "wimg", "lr", "mom",
+                 "dampening", "weight_decay", "nesterov", "step", "ticket", "cursor", "rng_offset", "apply_sgd",
+                 "loss_parts", "nparts", "loss_acc", "mfma_dtype", "dbg", "exch_id", "exch_timeout_s", "grad_post",
+                 "fc_part")
+TrainArgs, UpdateArgs = namedtuple("TrainArgs", TRAIN_FIELDS), namedtuple("UpdateArgs", UPDATE_FIELDS)
+_ENGINE = object()  # (default of a builder's ``cursor``: the engine's own device cursor)
 
 
 def native_max_steps() -> int:
@@ -184,9 +189,25 @@ class FusedLeNetTrainer:
             raise ValueError(f"global batch {global_batch} not divisible by world size {self.world}")
         self.global_batch = int(global_batch)
         self.B = self.global_batch // self.world
-        self.grid = int(grid) if grid else min(self.B, 256)
         if compute_dtype not in _native.MFMA_CODE:
             raise ValueError(f"compute dtype {compute_dtype}: expected bfloat16, float16 or float32")
+        lay = lenet_layout()
+        self.fp32 = compute_dtype == torch.float32
+        # batch staging (per-rank batch <= stage_max_batch, one workgroup per sample): lenet_update
+        # gathers the next step's pixels + labels one step ahead, so lenet_train starts with no
+        # dependent index chain.  Split step (lenet_fused.hip / lenet_fused_f32.hip KS > 1): split_k
+        # workgroups per sample share the backward conv stages; used whenever the whole grid fits
+        # one wave of the GPU (split_k * B <= 256 CUs).  CSED_SPLIT=0 keeps one workgroup per
+        # sample.  The exact-fp32 kernel gathers its samples itself and stages its batch only in
+        # the split step.
+        self.grid = int(grid) if grid else min(self.B, 256)
+        auto = os.environ.get("CSED_SPLIT", "auto").strip().lower() != "0"
+        can_stage = self.B <= lay.stage_max_batch and self.grid == self.B
+        self.split = (can_stage and grid is None and lay.split_k * self.B <= 256
+                      and (auto if split is None else bool(split)))
+        self.staged = can_stage and (not self.fp32 or self.split)
+        if self.split:
+            self.grid = lay.split_k * self.B
         self.lr, self.momentum, self.dampening = float(lr), float(momentum), float(dampening)
         self.weight_decay, self.nesterov = float(weight_decay), bool(nesterov)
         self.mfma = _native.MFMA_CODE[compute_dtype]
@@ -203,15 +224,14 @@ class FusedLeNetTrainer:
         if broadcast_init and self.world > 1:  # the DDP-constructor parameter sync (CS4)
             _comm.ctl_broadcast(self.ctx, self.flat.data, src=0)  # (RCCL, or the host over gloo)
         self.momentum_buf = _native.zeros(self.flat.data.shape, torch.float32, self.flat.data.device)
-        wimg_elems, conv_params, vec_len, stage_max = layout()
         # zero-initialised: padding rows / columns of the images must stay zero
-        self.wimg = _native.zeros(wimg_elems, torch.int16, dev)
+        self.wimg = _native.zeros(lay.wimg_elems, torch.int16, dev)
         # per-WG conv partial gradients and per-sample fc vectors (see lenet_fused.hip)
-        self.slab = torch.empty((self._max_grid(), conv_params), dtype=torch.float32, device=dev)
+        self.slab = torch.empty((self.grid, lay.conv_params), dtype=torch.float32, device=dev)
         # (fp32 [B, 464] for the exact-fp32 kernel; the 16-bit kernels keep raw 16-bit values
         # feature-major, [464, round_up(B, 64)], in the same bytes: fc_vectors() decodes either)
-        self.vslab = _native.zeros(((self.B + 63) // 64 * 64, vec_len), torch.float32, dev)
-        self.loss_parts = _native.zeros(2 * self._max_grid(), torch.float32, dev)
+        self.vslab = _native.zeros(((self.B + 63) // 64 * 64, lay.vec_len), torch.float32, dev)
+        self.loss_parts = _native.zeros(2 * self.grid, torch.float32, dev)
         self.loss_acc = _native.zeros(2, torch.float32, dev)  # running (loss sum, correct)
         self.step_count = _native.zeros(1, torch.long, dev)
         self.ticket = _native.zeros(1, torch.int32, dev)
@@ -219,35 +239,17 @@ class FusedLeNetTrainer:
         self.rng_offset = _native.zeros(1, torch.long, dev)
         self.eval_parts = _native.zeros(2 * 256, torch.float32, dev)
         self.perm = _native.arange(self.B, dev)
-        # batch staging (per-rank batch <= stage_max): lenet_update gathers the next step's
-        # pixels + labels one step ahead, so lenet_train starts with no dependent index chain
-        # (the exact-fp32 kernel, lenet_fused_f32.hip, gathers its samples itself)
-        self.fp32 = compute_dtype == torch.float32
         # split-K fc-gradient scratch (lenet_fused.hip fc_split_slices): per-rank batches > 1024
         # without the fused exchange form the fc weight gradients as up to 8 batch slices per
         # tile on all CUs, the tile's last slice finishing it (8 x 88 tiles x 256 partial sums,
         # then 88 arrival counters that must start at zero)
         self.fc_part = _native.zeros(8 * 88 * 256 + 128, torch.float32, dev) if self.B > 1024 else None
-        # split step (lenet_fused.hip / lenet_fused_f32.hip KS > 1): split_k workgroups per sample
-        # share the backward conv stages; used whenever the whole grid fits one wave of the GPU
-        # (split_k * B <= 256 CUs).  CSED_SPLIT=0 keeps one workgroup per sample.  The exact-fp32
-        # kernel stages its batch only in the split step.
-        split_k = split_factor()
-        auto = os.environ.get("CSED_SPLIT", "auto").strip().lower() != "0"
-        can_stage = self.B <= stage_max and self.grid == self.B
-        self.split = (can_stage and grid is None and split_k * self.B <= 256
-                      and (auto if split is None else bool(split)))
-        self.staged = can_stage and (not self.fp32 or self.split)
-        if self.split:
-            self.grid = split_k * self.B
-            self.slab = torch.empty((self._max_grid(), conv_params), dtype=torch.float32, device=dev)
-            self.loss_parts = _native.zeros(2 * self._max_grid(), torch.float32, dev)
         # one staging row per workgroup (split step: row r holds sample r % B)
-        # the sample-tile kernel (16-bit, per-rank batch >= tile_min_batch()) stages the first tile
-        # of every workgroup instead: grid * tile_samples() rows (csrc/kernels/lenet_tile.hip)
-        self.tile_staged = (not self.fp32 and not self.staged and self.B >= tile_min_batch()
+        # the sample-tile kernel (16-bit, per-rank batch >= tile_min_batch) stages the first tile
+        # of every workgroup instead: grid * tile_samples rows (csrc/kernels/lenet_tile.hip)
+        self.tile_staged = (not self.fp32 and not self.staged and self.B >= lay.tile_min_batch
                             and self.grid == tile_grid(self.B))
-        srows = self.grid if self.staged else (self.grid * tile_samples() if self.tile_staged else 0)
+        srows = self.grid if self.staged else (self.grid * lay.tile_samples if self.tile_staged else 0)
         self.xstage = _native.zeros((srows, 784), torch.uint8, dev) if srows else None
         self.lstage = _native.zeros(srows, torch.long, dev) if srows else None
         t_mark = time.perf_counter()
@@ -259,7 +261,7 @@ class FusedLeNetTrainer:
         self._stepper: tuple | None = None  # (key, csed.LenetStepper), see stepper()
         self.native_max = native_max_steps()
         # which training kernel runs a step: 0 auto (the sample-tile kernel, csrc/kernels/
-        # lenet_tile.hip, for 16-bit unstaged per-rank batches >= tile_min_batch()), 1 the
+        # lenet_tile.hip, for 16-bit unstaged per-rank batches >= tile_min_batch), 1 the
         # per-sample lenet_train, 2 the sample-tile kernel
         self.train_kernel = 0
         self._eval_cache: dict[int, tuple] = {}
@@ -288,15 +290,11 @@ class FusedLeNetTrainer:
             self.path_timing_us = donor.path_timing_us
             self.exchange_note = "fused exchange reused from the previous engine (opened and self-tested there)"
         elif multi:
-            from ..parallel.ipc import ranks_per_gpu
-
-            self._xdiag["ranks_per_gpu"] = ranks_per_gpu(self.ctx)  # (collective: every rank)
-        if donor is not None:
-            pass
-        elif multi and mode in ("auto", "fused"):
-            self._enable_exchange(required=(mode == "fused"))
-        elif multi:
-            self._xdiag["ipc_open"] = f"not tried (CSED_ALLREDUCE={mode})"
+            self._xdiag["ranks_per_gpu"] = _ipc.ranks_per_gpu(self.ctx)  # (collective: every rank)
+            if mode in ("auto", "fused"):
+                self._enable_exchange(required=(mode == "fused"))
+            else:
+                self._xdiag["ipc_open"] = f"not tried (CSED_ALLREDUCE={mode})"
         # Loopback exchange (one GPU, no process group): lenet_update runs its full push + poll
         # code for loopback_world - 1 virtual peers that are slots of this rank's own buffer
         # (csrc/comm ipc_open_loopback).  Each peer returns this rank's own gradient, and the
@@ -308,23 +306,13 @@ class FusedLeNetTrainer:
         if self.loopback_world:
             if self.world > 1:
                 raise ValueError("loopback_world is a one-GPU measurement mode (world size 1)")
-            self.exch = open_loopback_exchange(self.device, exch_words(), self.loopback_world)
+            self.exch = open_loopback_exchange(self.device, lay.exch_words, self.loopback_world)
             self.exchange_note = f"loopback exchange: {self.loopback_world} virtual ranks on one GPU"
 
     @property
     def grad_scale(self) -> float:
         """Loss-gradient scale of a full step: 1 / (global batch) (x 1 / loopback_world)."""
         return 1.0 / (self.global_batch * max(1, self.loopback_world))
-
-    # 16-bit steps run their backward at per-sample scale (dlogits = softmax - onehot, so fp16
-    # gradient images stay normal numbers at any batch) and lenet_update applies the 1 / (global
-    # batch) in fp32 (its grad_post); the exact-fp32 kernel takes the scale in-kernel.  For a
-    # power-of-two batch both give bit-identical bf16 results.
-    def _train_scale(self, grad_scale: float) -> float:
-        return grad_scale if self.fp32 else 1.0
-
-    def _post_scale(self, grad_scale: float) -> float:
-        return 1.0 if self.fp32 else grad_scale
 
     def _vec16(self, B: int) -> torch.Tensor:
         """The 16-bit kernels' fc-vector slab of a batch of B: raw [round_up(B, 64) / 4, 464, 4]
@@ -373,7 +361,7 @@ class FusedLeNetTrainer:
         t0 = time.perf_counter()
         xd = self._xdiag
         xd["peer_access"] = _ipc.peer_access(self.device)
-        ex, why = open_exchange(self.ctx, exch_words(), shared=self._xdiag.get("ranks_per_gpu"))
+        ex, why = open_exchange(self.ctx, lenet_layout().exch_words, shared=self._xdiag.get("ranks_per_gpu"))
         hook = _ipc.test_reject_hook()
         last = self.ctx.rank == self.ctx.world_size - 1
         if hook == "open":  # (test hook: the last rank's mapping "fails"; every rank votes)
@@ -502,9 +490,7 @@ class FusedLeNetTrainer:
 
         ops = torch.ops.csed
         pg_dev = _comm.ctl_device(self.ctx)
-        common = (self.flat.data, self.momentum_buf, self.wimg, self.lr, self.momentum, self.dampening,
-                  self.weight_decay, self.nesterov, self.step_count, self.ticket, None, None, False, None, 0, None,
-                  self.mfma)
+        raw = dict(with_loss=False, grad_scale=1.0)  # (plain slab sums; the local one without the split-K scratch)
         ok = True
         # every round's local and exchanged gradients first, then ONE process-group all-reduce of
         # all the local ones (a collective round trip per round was most of the self-test's time)
@@ -512,10 +498,9 @@ class FusedLeNetTrainer:
         fused = torch.empty_like(local)
         for r in range(rounds):
             ops.lenet_selftest_fill(self.slab, self.vslab, self.B, self.mfma, 977 + 31 * self.ctx.rank + 7919 * r)
-            ops.lenet_update(self.slab, self.grid, self.vslab, self.B, None, local[r], *common)
+            ops.lenet_update(*self.update_args("reduce", grad=local[r], exchange=False, fc_split=False, **raw))
             try:
-                ops.lenet_update(self.slab, self.grid, self.vslab, self.B, None, fused[r], *common, None,
-                                 self.exch.id, self.exch_timeout_s)
+                ops.lenet_update(*self.update_args("reduce", grad=fused[r], exchange=True, **raw))
             except Exception:
                 ok = False
         ref = local.to(pg_dev, copy=True)
@@ -596,9 +581,6 @@ class FusedLeNetTrainer:
         self._graphs.clear()
         self._stepper = None
 
-    def _max_grid(self) -> int:
-        return max(self.grid, 1)
-
     # ----------------------------------------------------------------- state
     def repack(self) -> None:
         """Rebuild the 16-bit weight images from the fp32 master parameters."""
@@ -639,18 +621,16 @@ class FusedLeNetTrainer:
             torch.ops.csed.lenet_stage(self.train_data.images, self.train_data.labels, self.perm, self.cursor,
                                        self.B, self.xstage, self.lstage)
 
-
-
     def uses_tile_kernel(self, B: int | None = None, grid: int | None = None) -> bool:
         """Whether a full step of per-rank batch B on ``grid`` workgroups runs the sample-tile kernel
         (csrc/kernels/lenet_tile.hip) -- the launcher's own rule (bindings.cpp lenet_train) for
-        kernel_for()'s choice: 16-bit, and kernel 2, or kernel 0 (auto) with B >= tile_min_batch()."""
+        kernel_for()'s choice: 16-bit, and kernel 2, or kernel 0 (auto) with B >= tile_min_batch."""
         B = self.B if B is None else B
         grid = self.grid if grid is None else grid
         if self.fp32:
             return False
         k = self.kernel_for(B, grid)
-        return k == 2 or (k == 0 and B >= tile_min_batch())
+        return k == 2 or (k == 0 and B >= lenet_layout().tile_min_batch)
 
     @property
     def kernel_names(self) -> str:
@@ -671,32 +651,71 @@ class FusedLeNetTrainer:
         return self.perm.numel() // self.B
 
     # ------------------------------------------------------------ launches
-    def _launch_step(self, B: int, grid: int, grad_scale: float, cursor: torch.Tensor | None,
-                     perm: torch.Tensor) -> None:
+    def train_args(self, *, B=None, grid=None, perm=None, cursor=_ENGINE, grad_scale=None, rank=None, dbg=None,
+                   stage_next=False, staged=None, scale_in_kernel=None) -> TrainArgs:
+        """The arguments of ``csed::lenet_train`` (TRAIN_FIELDS), by default the engine's full step: B samples
+        at ``cursor`` in ``perm`` (``cursor=None``: perm's first B) on ``grid`` workgroups of kernel_for()'s
+        kernel.  ``staged``: read the batch from the staging buffers (default: where that kernel stages a
+        batch of the engine's own grid at a cursor); ``stage_next``: a staged launch gathers the next batch.
+        ``grad_scale``: the step's loss-gradient scale.  16-bit steps run their backward at per-sample scale
+        (dlogits = softmax - onehot, so fp16 gradient images stay normal numbers at any batch) and
+        lenet_update applies it in fp32 (grad_post); the exact-fp32 kernel takes it in-kernel
+        (``scale_in_kernel``).  For a power-of-two batch both give bit-identical bf16 results."""
+        B, grid = self.B if B is None else B, self.grid if grid is None else grid
+        cursor = self.cursor if cursor is _ENGINE else cursor
+        kernel = self.kernel_for(B, grid)
+        if staged is None:  # (the epoch's short tail, or a launch on another grid, reads perm)
+            staged = self._stages(kernel) and cursor is not None and grid == self.grid
+        grad_scale = self.grad_scale if grad_scale is None else grad_scale
+        in_kernel = self.fp32 if scale_in_kernel is None else scale_in_kernel
+        return TrainArgs(
+            images=self.train_data.images, labels=self.train_data.labels, perm=self.perm if perm is None else perm,
+            cursor=cursor, B=B, rank=self.ctx.rank if rank is None else rank, wimg=self.wimg, params=self.flat.data,
+            slab=self.slab, vslab=self.vslab, loss_parts=self.loss_parts, grad_scale=grad_scale if in_kernel else 1.0,
+            mean=MNIST_MEAN, std=MNIST_STD, drop_p=self.drop_p, seed=self.seed, rng_offset=self.rng_offset, grid=grid,
+            mfma_dtype=self.mfma, dbg=dbg, xstage=self.xstage if staged else None,
+            lstage=self.lstage if staged else None, stage_next=bool(stage_next and staged), kernel=kernel)
+
+    def update_args(self, mode: str, *, B=None, grid=None, cursor=_ENGINE, grad=None, grad_scale=None, exchange=None,
+                    dbg=None, with_loss=True, fc_split=None, scale_in_kernel=None) -> UpdateArgs:
+        """The arguments of ``csed::lenet_update`` (UPDATE_FIELDS).  ``mode``: "step" (reduce the slabs, then
+        SGD, in one kernel), "reduce" (reduce only, into ``grad``; advances neither cursor nor Philox offset)
+        or "apply" (SGD from the already reduced ``grad``).  The kernel that reduces also sums the loss
+        partials (``with_loss``), applies the 16-bit steps' ``grad_scale`` (train_args), runs the fused
+        exchange (``exchange``; default: where the engine has one) and, by default exactly without it, gets
+        the split-K fc scratch of per-rank batches > 1024 (``fc_split``)."""
+        if mode not in ("step", "reduce", "apply") or (grad is None) != (mode == "step"):
+            raise ValueError(f"lenet_update mode {mode!r}: 'step', or 'reduce' / 'apply' with grad=")
+        B, grid = self.B if B is None else B, self.grid if grid is None else grid
+        reduces, advances = mode != "apply", mode != "reduce"
+        exch = self.exch if reduces and (self.exch is not None if exchange is None else exchange) else None
+        loss = reduces and with_loss
+        grad_scale = self.grad_scale if grad_scale is None else grad_scale
+        in_kernel = self.fp32 if scale_in_kernel is None else scale_in_kernel
+        fc_split = (reduces and exch is None) if fc_split is None else fc_split
+        return UpdateArgs(
+            slab=self.slab, grid=grid, vslab=self.vslab, B=B, grad_in=grad if mode == "apply" else None,
+            grad_out=grad if mode == "reduce" else None, params=self.flat.data, momentum=self.momentum_buf,
+            wimg=self.wimg, lr=self.lr, mom=self.momentum, dampening=self.dampening, weight_decay=self.weight_decay,
+            nesterov=self.nesterov, step=self.step_count, ticket=self.ticket,
+            cursor=(self.cursor if cursor is _ENGINE else cursor) if advances else None,
+            rng_offset=self.rng_offset if advances else None, apply_sgd=advances,
+            loss_parts=self.loss_parts if loss else None, nparts=grid if loss else 0,
+            loss_acc=self.loss_acc if loss else None, mfma_dtype=self.mfma, dbg=dbg,
+            exch_id=-1 if exch is None else exch.id, exch_timeout_s=2.0 if exch is None else self.exch_timeout_s,
+            grad_post=grad_scale if reduces and not in_kernel else 1.0, fc_part=self.fc_part if fc_split else None)
+
+    def _launch_step(self, perm: torch.Tensor, **kw) -> None:
+        """A step's launches on ``perm``; ``kw``: B, grid, cursor, grad_scale where not the full step's."""
         ops = torch.ops.csed
         # full steps read the staged batch and stage the next one; the epoch's short tail uses perm
-        kern = self.kernel_for(B, grid)
-        st = self._stages(kern) and cursor is not None
-        ops.lenet_train(self.train_data.images, self.train_data.labels, perm, cursor, B, self.ctx.rank, self.wimg,
-                        self.flat.data, self.slab, self.vslab, self.loss_parts, self._train_scale(grad_scale),
-                        MNIST_MEAN, MNIST_STD, self.drop_p, self.seed, self.rng_offset, grid, self.mfma, None,
-                        self.xstage if st else None, self.lstage if st else None, st, kern)
-        common = (self.flat.data, self.momentum_buf, self.wimg, self.lr, self.momentum, self.dampening,
-                  self.weight_decay, self.nesterov, self.step_count, self.ticket)
-        post = self._post_scale(grad_scale)
-        if self.exch is not None:
-            ops.lenet_update(self.slab, grid, self.vslab, B, None, None, *common, cursor, self.rng_offset, True,
-                             self.loss_parts, grid, self.loss_acc, self.mfma, None, self.exch.id, self.exch_timeout_s,
-                             post)
-        elif self.comm:
-            ops.lenet_update(self.slab, grid, self.vslab, B, None, self.flat.grad, *common, None, None, False,
-                             self.loss_parts, grid, self.loss_acc, self.mfma, None, -1, 2.0, post, self.fc_part)
-            dist.all_reduce(self.flat.grad, op=dist.ReduceOp.SUM)
-            ops.lenet_update(self.slab, grid, self.vslab, B, self.flat.grad, None, *common, cursor, self.rng_offset,
-                             True, None, 0, None, self.mfma)
+        ops.lenet_train(*self.train_args(perm=perm, stage_next=True, **kw))
+        if self.exch is not None or not self.comm:  # one kernel: the fused exchange, or no exchange at all
+            ops.lenet_update(*self.update_args("step", **kw))
         else:
-            ops.lenet_update(self.slab, grid, self.vslab, B, None, None, *common, cursor, self.rng_offset, True,
-                             self.loss_parts, grid, self.loss_acc, self.mfma, None, -1, 2.0, post, self.fc_part)
+            ops.lenet_update(*self.update_args("reduce", grad=self.flat.grad, **kw))
+            dist.all_reduce(self.flat.grad, op=dist.ReduceOp.SUM)
+            ops.lenet_update(*self.update_args("apply", grad=self.flat.grad, **kw))
 
     def _stages(self, kernel: int) -> bool:
         """Whether a full step launched with ``kernel`` (kernel_for) reads / writes the staging
@@ -707,9 +726,9 @@ class FusedLeNetTrainer:
 
     def kernel_for(self, B: int, grid: int) -> int:
         """``train_kernel`` for a launch of per-rank batch B on ``grid`` workgroups: the tile kernel
-        only where its grid (min(256, ceil(B / tile_samples()))) is the launch's, else per-sample."""
+        only where its grid (min(256, ceil(B / tile_samples))) is the launch's, else per-sample."""
         if self.train_kernel == 0:
-            return 0 if (B < tile_min_batch() or grid == tile_grid(B)) else 1
+            return 0 if (B < lenet_layout().tile_min_batch or grid == tile_grid(B)) else 1
         if self.train_kernel == 2 and grid != tile_grid(B):
             return 1
         return self.train_kernel
@@ -718,25 +737,15 @@ class FusedLeNetTrainer:
         """Mean-loss gradient of the batch at the cursor, without updating anything
         (lenet_train + the reduce-only lenet_update).  Also accumulates the batch's
         loss / correct count into the running totals."""
-        grid = grid or self.grid
+        kw = dict(grid=grid or self.grid, grad_scale=1.0 / self.global_batch)  # (no loopback factor: no exchange)
         g = torch.empty(N_PARAMS, dtype=torch.float32, device=self.device)
-        ops = torch.ops.csed
-        ops.lenet_train(self.train_data.images, self.train_data.labels, self.perm, self.cursor, self.B, self.ctx.rank,
-                        self.wimg, self.flat.data, self.slab, self.vslab, self.loss_parts,
-                        self._train_scale(1.0 / self.global_batch),
-                        MNIST_MEAN, MNIST_STD, self.drop_p, self.seed, self.rng_offset, grid, self.mfma, dbg,
-                        self.xstage if self._stages(self.kernel_for(self.B, grid)) and grid == self.grid else None,
-                        self.lstage if self._stages(self.kernel_for(self.B, grid)) and grid == self.grid else None, False,
-                        self.kernel_for(self.B, grid))
-        ops.lenet_update(self.slab, grid, self.vslab, self.B, None, g, self.flat.data, self.momentum_buf, self.wimg,
-                         self.lr, self.momentum, self.dampening, self.weight_decay, self.nesterov, self.step_count,
-                         self.ticket, None, None, False, self.loss_parts, grid, self.loss_acc, self.mfma, None, -1,
-                         2.0, self._post_scale(1.0 / self.global_batch), self.fc_part)
+        torch.ops.csed.lenet_train(*self.train_args(dbg=dbg, **kw))
+        torch.ops.csed.lenet_update(*self.update_args("reduce", grad=g, exchange=False, **kw))
         return g
 
     def step(self) -> None:
         """One full-batch training step at the device cursor (eager launches)."""
-        self._launch_step(self.B, self.grid, self.grad_scale, self.cursor, self.perm)
+        self._launch_step(self.perm)
 
     def tail_size(self) -> int:
         """Per-rank samples of the epoch's short last batch (0 if the epoch divides evenly)."""
@@ -746,7 +755,7 @@ class FusedLeNetTrainer:
         rem = self.tail_size()
         tail = self.perm[self.full_steps() * self.B:]  # a view: stable pointer for graph replay
         gb = rem * self.world * max(1, self.loopback_world)  # (the sampler pads to a multiple: same on every rank)
-        self._launch_step(rem, min(rem, self.grid), 1.0 / gb, None, tail)
+        self._launch_step(tail, B=rem, grid=min(rem, self.grid), cursor=None, grad_scale=1.0 / gb)
         # the tail step does not use the cursor; keep it consistent for the next epoch
         torch.ops.csed.lenet_add_(self.cursor, 1)
 
@@ -910,22 +919,12 @@ class FusedLeNetTrainer:
         C++.  None where a step is more than two launches (the all-reduce fallback)."""
         if self.comm and self.exch is None:
             return None
-        exch_id = -1 if self.exch is None else self.exch.id
-        key = (self.perm.data_ptr(), exch_id, self.staged, self.train_kernel)
-        st_ok = self._stages(self.kernel_for(self.B, self.grid))
+        key = (self.perm.data_ptr(), -1 if self.exch is None else self.exch.id, self.staged, self.train_kernel)
         if self._stepper is None or self._stepper[0] != key:
             st = torch.classes.csed.LenetStepper()
-            st.set_train(self.train_data.images, self.train_data.labels, self.perm, self.cursor, self.B,
-                         self.ctx.rank, self.wimg, self.flat.data, self.slab, self.vslab, self.loss_parts,
-                         self._train_scale(self.grad_scale), MNIST_MEAN, MNIST_STD, self.drop_p, self.seed,
-                         self.rng_offset,
-                         self.grid, self.mfma, self.xstage if st_ok else None,
-                         self.lstage if st_ok else None, st_ok, self.kernel_for(self.B, self.grid))
-            st.set_update(self.slab, self.grid, self.vslab, self.B, self.flat.data, self.momentum_buf, self.wimg,
-                          self.lr, self.momentum, self.dampening, self.weight_decay, self.nesterov,
-                          self.step_count, self.ticket, self.cursor, self.rng_offset, self.loss_parts, self.grid,
-                          self.loss_acc, self.mfma, exch_id, self.exch_timeout_s if exch_id >= 0 else 2.0,
-                          self._post_scale(self.grad_scale), self.fc_part)
+            st.set_train(*self.train_args(stage_next=True))
+            # (the split-K fc scratch also next to the exchange, where the launcher does not use it)
+            st.set_update(*self.update_args("step", fc_split=True))
             self._stepper = (key, st)
         return self._stepper[1]
 

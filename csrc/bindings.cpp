@@ -593,10 +593,10 @@ void wgrad_reduce(const Tensor& ws, Tensor& dw, const optional<Tensor>& db, int6
 }
 
 // ----------------------------------------------------------- fused lenet
-// Buffer sizes the fused LeNet kernels expect: [weight-image elements, conv
-// slab row (floats per workgroup), per-sample vector length, flat params,
-// largest per-rank batch the batch-staging path handles, exchange words per sender,
-// workgroups per sample of the split step].
+// Buffer sizes the fused LeNet kernels expect: [weight-image elements, conv slab row (floats per
+// workgroup), per-sample vector length, flat params, largest per-rank batch the batch-staging path
+// handles, exchange words per sender, workgroups per sample of the split step, samples per tile of
+// the sample-tile kernel, smallest per-rank batch the auto mode runs on it] (engine/fused.py LenetLayout).
 std::vector<int64_t> lenet_layout() {
   return {csed::lenet_wimg_elems(), csed::lenet_conv_param_count(), csed::lenet_vec_len(),
           csed::lenet_param_count(), csed::lenet_stage_max_batch(), csed::lenet_exch_words(),
@@ -852,11 +852,6 @@ void lenet_eval(const Tensor& images, const Tensor& labels, const Tensor& order,
                                     lcode(mfma_dtype), cur_stream(images), (int)kernel));
 }
 
-// Native step executor: the two launches of a full-batch training step (lenet_train +
-// single-kernel lenet_update: local SGD, or the fused exchange), argument blocks built and
-// checked once, then `run(k)` enqueues the 2k launches on the current stream from C++.  A
-// short run (the driver's 20-step window) pays no graph-launch setup and no Python per
-// launch; long runs use the captured graphs (engine/fused.py:step_plan picks).
 // A HIP graph of the work this host thread enqueues on the current stream of `device` between
 // begin() and end() (hipStreamBeginCapture in thread-local mode: another thread's unsafe call -- a
 // process group watchdog's event query -- does not invalidate it), instantiated at end(), replayed
@@ -935,43 +930,47 @@ struct HipGraph : torch::CustomClassHolder {
   }
 };
 
+// Native step executor: the two launches of a full-batch training step (lenet_train + single-kernel lenet_update:
+// local SGD, or the fused exchange), argument blocks built and checked once from exactly the two ops' argument
+// lists, then `run(k)` enqueues the 2k launches on the current stream from C++.  A short run (the driver's 20-step
+// window) pays no graph-launch setup and no Python per launch; long runs replay graphs (engine/fused.py:step_plan).
 struct LenetStepper : torch::CustomClassHolder {
   csed::LenetTrainArgs ta{};
   csed::LenetUpdateArgs ua{};
-  float* loss_parts = nullptr;
-  float* loss_acc = nullptr;
+  float *loss_parts = nullptr, *loss_acc = nullptr;  // (the update launcher takes these apart from ua)
   int64_t nparts = 0;
   csed::comm::IpcPeers px{};  // the exchange buffer's device view (ua.exch_id >= 0)
   int device = -1;
-  std::vector<Tensor> keep_t, keep_u;  // every tensor the argument blocks point into stays alive
+  std::vector<optional<Tensor>> keep_t, keep_u;  // every tensor the argument blocks point into stays alive
 
-  void set_train(Tensor images, Tensor labels, Tensor perm, Tensor cursor, int64_t B, int64_t rank, Tensor wimg,
-                 Tensor params, Tensor slab, Tensor vslab, Tensor loss_parts_t, double grad_scale, double mean,
-                 double std_, double drop_p, int64_t seed, Tensor rng_offset, int64_t grid, int64_t mfma_dtype,
-                 optional<Tensor> xstage, optional<Tensor> lstage, bool stage_next, int64_t kernel) {
+  void set_train(Tensor images, Tensor labels, Tensor perm, optional<Tensor> cursor, int64_t B, int64_t rank,
+                 Tensor wimg, Tensor params, Tensor slab, Tensor vslab, Tensor loss_parts_t, double grad_scale,
+                 double mean, double std_, double drop_p, int64_t seed, optional<Tensor> rng_offset, int64_t grid,
+                 int64_t mfma_dtype, optional<Tensor> dbg, optional<Tensor> xstage, optional<Tensor> lstage,
+                 bool stage_next, int64_t kernel) {
     ta = train_args(images, labels, perm, cursor, B, rank, wimg, params, slab, vslab, loss_parts_t, grad_scale,
-                    mean, std_, drop_p, seed, rng_offset, grid, mfma_dtype, c10::nullopt, xstage, lstage,
-                    stage_next, kernel);
+                    mean, std_, drop_p, seed, rng_offset, grid, mfma_dtype, dbg, xstage, lstage, stage_next, kernel);
     device = images.device().index();
-    keep_t = {images, labels, perm, cursor, wimg, params, slab, vslab, loss_parts_t, rng_offset};
-    if (xstage.has_value()) keep_t.insert(keep_t.end(), {*xstage, *lstage});
+    keep_t = {images, labels, perm, cursor, wimg, params, slab, vslab, loss_parts_t, rng_offset, dbg, xstage, lstage};
   }
 
-  void set_update(Tensor slab, int64_t grid, Tensor vslab, int64_t B, Tensor params, Tensor momentum, Tensor wimg,
-                  double lr, double mom, double dampening, double weight_decay, bool nesterov, Tensor step,
-                  Tensor ticket, Tensor cursor, Tensor rng_offset, Tensor loss_parts_t, int64_t nparts_,
-                  Tensor loss_acc_t, int64_t mfma_dtype, int64_t exch_id, double exch_timeout_s, double grad_post,
-                  optional<Tensor> fc_part) {
-    ua = update_args(slab, grid, vslab, B, c10::nullopt, c10::nullopt, params, momentum, wimg, lr, mom, dampening,
-                     weight_decay, nesterov, step, ticket, cursor, rng_offset, true, loss_parts_t, loss_acc_t,
-                     mfma_dtype, c10::nullopt, exch_id, exch_timeout_s, grad_post, fc_part);
-    loss_parts = loss_parts_t.data_ptr<float>();
-    loss_acc = loss_acc_t.data_ptr<float>();
+  void set_update(Tensor slab, int64_t grid, Tensor vslab, int64_t B, optional<Tensor> grad_in,
+                  optional<Tensor> grad_out, Tensor params, Tensor momentum, Tensor wimg, double lr, double mom,
+                  double dampening, double weight_decay, bool nesterov, Tensor step, Tensor ticket,
+                  optional<Tensor> cursor, optional<Tensor> rng_offset, bool apply_sgd, optional<Tensor> loss_parts_t,
+                  int64_t nparts_, optional<Tensor> loss_acc_t, int64_t mfma_dtype, optional<Tensor> dbg,
+                  int64_t exch_id, double exch_timeout_s, double grad_post, optional<Tensor> fc_part) {
+    TORCH_CHECK(apply_sgd && !grad_in && !grad_out && cursor, "LenetStepper: set_update takes a full step at a cursor");
+    ua = update_args(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
+                     nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts_t, loss_acc_t, mfma_dtype, dbg,
+                     exch_id, exch_timeout_s, grad_post, fc_part);
+    loss_parts = optpt<float>(loss_parts_t);
+    loss_acc = optpt<float>(loss_acc_t);
     nparts = nparts_;
     px = {};
     if (exch_id >= 0) CHECK_HIP(csed::comm::ipc_peers((int)exch_id, &px));  // once, not per launch
-    keep_u = {slab, vslab, params, momentum, wimg, step, ticket, cursor, rng_offset, loss_parts_t, loss_acc_t};
-    if (fc_part.has_value()) keep_u.push_back(*fc_part);
+    keep_u = {slab,   vslab,      params,       momentum,   wimg, step,   ticket,
+              cursor, rng_offset, loss_parts_t, loss_acc_t, dbg,  fc_part};
   }
 
   void run(int64_t k) {

@@ -55,10 +55,13 @@ def test_exchange_buffer_layout():
 
     if not _native.load(build_if_missing=False):
         pytest.skip("native extension not built")
-    layout = [int(v) for v in torch.ops.csed.lenet_layout()]
-    conv_pad, nparams, words = layout[1], layout[3], layout[5]
-    assert nparams == 21840 and conv_pad == 5376 and layout[6] == 4  # split step: 4 workgroups / sample
-    assert len(layout) == 9 and layout[7] == 4 and layout[8] == 1024  # sample tiles of 4 from batch 1024
+    from csed_514_project_distributed_training_using_pytorch_amd.engine.fused import lenet_layout
+
+    layout = lenet_layout()
+    conv_pad, nparams, words = layout.conv_params, layout.n_params, layout.exch_words
+    assert nparams == 21840 and conv_pad == 5376 and layout.split_k == 4  # split step: 4 workgroups / sample
+    # sample tiles of 4 from batch 1024
+    assert len(layout) == 9 and layout.tile_samples == 4 and layout.tile_min_batch == 1024
     fc_tiles = 4 * 21 + 4  # fc1: 4 x 21 tiles of [dW1 | db1], fc2: 4 tiles of [dW2 | db2]
     assert words == conv_pad + fc_tiles * 256 == 27904
     assert words % 4 == 0  # the IPC buffers are allocated in multiples of 4 words

@@ -97,9 +97,7 @@ def test_mask_statistics_steps_and_ranks():
         same_step = torch.cat([(d2 == d2b).flatten(), (d1 == d1b).flatten()]).float().mean().item()
         # rank 1, step 0: the same kernel launched with rank id 1 on the same batch
         eng.rng_offset.fill_(0)
-        ops.lenet_train(eng.train_data.images, eng.train_data.labels, eng.perm, eng.cursor, B, 1, eng.wimg,
-                        eng.flat.data, eng.slab, eng.vslab, eng.loss_parts, 1.0 / B, MNIST_MEAN, MNIST_STD, p,
-                        99, eng.rng_offset, eng.grid, eng.mfma, None, None, None, False)
+        ops.lenet_train(*eng.train_args(rank=1, staged=False, grad_scale=1.0 / B, scale_in_kernel=True))
         torch.cuda.synchronize()
         v = eng.fc_vectors(B).cpu()
         r2 = (v[:, V_P2:V_P2 + 320].view(B, 20, 16) != 0).any(2)

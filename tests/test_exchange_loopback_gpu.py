@@ -31,16 +31,14 @@ def test_loopback_exchange_returns_world_copies(world, B):
     eng = _engine(B, loopback_world=world)
     ops = torch.ops.csed
     gen = torch.Generator(device="cpu").manual_seed(5 + world + B)
-    common = (eng.flat.data, eng.momentum_buf, eng.wimg, eng.lr, eng.momentum, eng.dampening, eng.weight_decay,
-              eng.nesterov, eng.step_count, eng.ticket, None, None, False, None, 0, None, eng.mfma)
+    raw = dict(with_loss=False, grad_scale=1.0)  # (the plain slab sums)
     for _ in range(4):
         eng.slab.copy_(torch.randint(-8, 9, eng.slab.shape, generator=gen, dtype=torch.float32))
         eng.set_fc_vectors(torch.randint(-4, 5, (eng.B, 464), generator=gen, dtype=torch.float32))
         local = torch.empty(N_PARAMS, device=eng.device)
         fused = torch.empty_like(local)
-        ops.lenet_update(eng.slab, eng.grid, eng.vslab, eng.B, None, local, *common)
-        ops.lenet_update(eng.slab, eng.grid, eng.vslab, eng.B, None, fused, *common, None, eng.exch.id,
-                         eng.exch_timeout_s)
+        ops.lenet_update(*eng.update_args("reduce", grad=local, exchange=False, **raw))
+        ops.lenet_update(*eng.update_args("reduce", grad=fused, exchange=True, **raw))
         torch.cuda.synchronize()
         assert torch.equal(fused, local * world)
     assert eng.comm_errors() == 0
@@ -117,16 +115,13 @@ def test_loopback_mismatch_is_detected():
     muted, must raise the mismatch bit (not the timeout bit) and record the first bad word."""
     eng = _engine(8, loopback_world=4)
     ops = torch.ops.csed
-    common = (eng.flat.data, eng.momentum_buf, eng.wimg, eng.lr, eng.momentum, eng.dampening, eng.weight_decay,
-              eng.nesterov, eng.step_count, eng.ticket, None, None, False, None, 0, None, eng.mfma)
     eng.slab.fill_(1.0)
     eng.set_fc_vectors(torch.ones(eng.B, 464))
     poison = 0x7FC0BEEF  # a NaN no gradient produces
     ops.ipc_poison(eng.exch.id, 1, poison)  # fresh buffer: every workgroup's first tag is 1
     eng.exch.mute(True)
     out = torch.empty(N_PARAMS, device=eng.device)
-    ops.lenet_update(eng.slab, eng.grid, eng.vslab, eng.B, None, out, *common, None, eng.exch.id,
-                     eng.exch_timeout_s)
+    ops.lenet_update(*eng.update_args("reduce", grad=out, exchange=True, with_loss=False, grad_scale=1.0))
     torch.cuda.synchronize()
     err, diag = eng.comm_errors(), eng.comm_diag()
     assert err == eng.exch.ERR_MISMATCH, err

@@ -145,7 +145,7 @@ def test_tile_epoch_tail_on_the_tile_kernel():
     """An epoch whose short last batch is itself a large batch (per-rank batch 2048, tail 1500 >=
     tile_min_batch()): the tail step runs on the tile kernel (its unstaged path: no cursor, no
     staging rows), and the epoch stays within the 16-bit band of the per-sample kernel's."""
-    from csed_514_project_distributed_training_using_pytorch_amd.engine.fused import tile_grid, tile_min_batch
+    from csed_514_project_distributed_training_using_pytorch_amd.engine.fused import lenet_layout, tile_grid
 
     B, n = 2048, 2 * 2048 + 1500
     train = synthetic_mnist(n, seed=5)
@@ -157,7 +157,7 @@ def test_tile_epoch_tail_on_the_tile_kernel():
         rem = n - 2 * B
         g = torch.Generator().manual_seed(0)
         eng.train_epoch(torch.randperm(n, generator=g), steps_per_graph=2)
-        assert eng.tail_size() == rem and rem >= tile_min_batch()
+        assert eng.tail_size() == rem and rem >= lenet_layout().tile_min_batch
         if kernel == 0:  # the tail launch (B = rem, grid = min(rem, eng.grid)) takes the tile kernel
             assert eng.kernel_for(rem, min(rem, eng.grid)) == 0 and tile_grid(rem) == min(rem, eng.grid)
         torch.cuda.synchronize()

@@ -68,13 +68,9 @@ def main():
             eng.set_epoch_order(torch.randperm(len(data)))
             eng.step()
             torch.cuda.synchronize()
-            common = (eng.flat.data, eng.momentum_buf, eng.wimg, eng.lr, eng.momentum, eng.dampening,
-                      eng.weight_decay, eng.nesterov, eng.step_count, eng.ticket)
-            xid = eng.exch.id if eng.exch is not None else -1
 
-            def upd(dbg=None):
-                ops.lenet_update(eng.slab, eng.grid, eng.vslab, B, None, None, *common, None, None, True,
-                                 eng.loss_parts, eng.grid, eng.loss_acc, eng.mfma, dbg, xid, eng.exch_timeout_s)
+            def upd(dbg=None):  # the step's update alone: no cursor to move, nothing scaled, no split-K fc scratch
+                ops.lenet_update(*eng.update_args("step", cursor=None, dbg=dbg, scale_in_kernel=True, fc_split=False))
 
             t_upd = timeit(upd)
             t_step = step_us(eng)

@@ -23,29 +23,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from csed_514_project_distributed_training_using_pytorch_amd.data import synthetic_mnist  # noqa: E402
-from csed_514_project_distributed_training_using_pytorch_amd.data.mnist import MNIST_MEAN, MNIST_STD  # noqa: E402
 from csed_514_project_distributed_training_using_pytorch_amd.engine.fused import (  # noqa: E402
-    FusedLeNetTrainer, tile_grid, tile_min_batch)
+    FusedLeNetTrainer, lenet_layout, tile_grid)
 from csed_514_project_distributed_training_using_pytorch_amd.models import Net  # noqa: E402
 
 
 def stamped_graph(eng, nsteps, dt, du):
     ops = torch.ops.csed
-    B, grid = eng.B, eng.grid
-    kern = eng.kernel_for(B, grid)
-    st = eng._stages(kern)
-    common = (eng.flat.data, eng.momentum_buf, eng.wimg, eng.lr, eng.momentum, eng.dampening,
-              eng.weight_decay, eng.nesterov, eng.step_count, eng.ticket)
-    xid = eng.exch.id if eng.exch is not None else -1
 
-    def step(i):
-        ops.lenet_train(eng.train_data.images, eng.train_data.labels, eng.perm, eng.cursor, B, 0, eng.wimg,
-                        eng.flat.data, eng.slab, eng.vslab, eng.loss_parts, eng._train_scale(eng.grad_scale),
-                        MNIST_MEAN, MNIST_STD, eng.drop_p, eng.seed, eng.rng_offset, grid, eng.mfma, dt[i],
-                        eng.xstage if st else None, eng.lstage if st else None, st, kern)
-        ops.lenet_update(eng.slab, grid, eng.vslab, B, None, None, *common, eng.cursor, eng.rng_offset, True,
-                         eng.loss_parts, grid, eng.loss_acc, eng.mfma, du[i], xid, eng.exch_timeout_s,
-                         eng._post_scale(eng.grad_scale), eng.fc_part)
+    def step(i):  # the engine's full step, stamped (the split-K fc scratch also next to the exchange)
+        ops.lenet_train(*eng.train_args(stage_next=True, dbg=dt[i]))
+        ops.lenet_update(*eng.update_args("step", dbg=du[i], fc_split=True))
 
     g = torch.cuda.CUDAGraph()
     s = torch.cuda.Stream()
@@ -98,7 +86,7 @@ def main():
             dt = torch.zeros(n, eng.grid * 32, dtype=torch.long, device=dev)
             du = torch.zeros(n, 8 * 1024, dtype=torch.long, device=dev)
             kern = eng.kernel_for(B, eng.grid)
-            tile = B >= tile_min_batch() and kern != 1 and eng.grid == tile_grid(B)
+            tile = B >= lenet_layout().tile_min_batch and kern != 1 and eng.grid == tile_grid(B)
             i_in, i_out = (12, 13) if tile else (22, 23)
             # fc_blocks(B) (lenet_fused.hip): 88 FC tiles, 8 / waves-per-tile of them per block
             wpt = 1 if B <= 128 else 2 if B <= 256 else 4 if B <= 512 else 8

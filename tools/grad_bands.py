@@ -32,17 +32,11 @@ for B in (64, 1024, 8192):
         eng.set_epoch_order(order)
         g = eng.gradient().cpu()
         # the same batch with the round-1..3 scaling: 1 / B inside the 16-bit backward
-        kern = eng.kernel_for(B, eng.grid)
-        st = eng._stages(kern)
         ops = torch.ops.csed
-        ops.lenet_train(eng.train_data.images, eng.train_data.labels, eng.perm, eng.cursor, B, 0, eng.wimg,
-                        eng.flat.data, eng.slab, eng.vslab, eng.loss_parts, 1.0 / B, MNIST_MEAN, MNIST_STD, 0.0,
-                        eng.seed, eng.rng_offset, eng.grid, eng.mfma, None, eng.xstage if st else None,
-                        eng.lstage if st else None, False, kern)
+        ops.lenet_train(*eng.train_args(scale_in_kernel=True))
         g_pre = torch.empty_like(eng.flat.data)
-        ops.lenet_update(eng.slab, eng.grid, eng.vslab, B, None, g_pre, eng.flat.data, eng.momentum_buf, eng.wimg,
-                         eng.lr, eng.momentum, eng.dampening, eng.weight_decay, eng.nesterov, eng.step_count,
-                         eng.ticket, None, None, False, None, 0, None, eng.mfma)
+        ops.lenet_update(*eng.update_args("reduce", grad=g_pre, with_loss=False, scale_in_kernel=True,
+                                          fc_split=False))
         g_pre = g_pre.cpu()
         x = ((data.images[order].float() / 255.0 - MNIST_MEAN) / MNIST_STD).to(dt).float().view(-1, 1, 28, 28)
         ref.eval()

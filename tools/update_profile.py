@@ -6,7 +6,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from csed_514_project_distributed_training_using_pytorch_amd.data import synthetic_mnist  # noqa: E402
-from csed_514_project_distributed_training_using_pytorch_amd.data.mnist import MNIST_MEAN, MNIST_STD  # noqa: E402
 from csed_514_project_distributed_training_using_pytorch_amd.engine.fused import FusedLeNetTrainer  # noqa: E402
 from csed_514_project_distributed_training_using_pytorch_amd.models import Net  # noqa: E402
 
@@ -35,25 +34,21 @@ def main():
     ops = torch.ops.csed
     g = torch.empty(21840, device=dev)
 
+    # the kernels alone: the batch at the (unmoved) cursor with 1 / B inside the backward, the next one not
+    # staged; updates that move no cursor, scale nothing and do not take the split-K fc scratch
+    alone = dict(scale_in_kernel=True, fc_split=False)
+
     def train():
-        ops.lenet_train(eng.train_data.images, eng.train_data.labels, eng.perm, eng.cursor, B, 0, eng.wimg,
-                        eng.flat.data, eng.slab, eng.vslab, eng.loss_parts, 1.0 / B, MNIST_MEAN, MNIST_STD, 0.5, 1,
-                        eng.rng_offset, eng.grid, eng.mfma, None, eng.xstage, eng.lstage, False)
+        ops.lenet_train(*eng.train_args(stage_next=False, scale_in_kernel=True))
 
-    common = lambda: (eng.flat.data, eng.momentum_buf, eng.wimg, 0.01, 0.5, 0.0, 0.0, False, eng.step_count,
-                      eng.ticket)
-
-    def upd_full():
-        ops.lenet_update(eng.slab, eng.grid, eng.vslab, B, None, None, *common(), None, None, True, eng.loss_parts,
-                         eng.grid, eng.loss_acc, eng.mfma)
+    def upd_full(dbg=None):
+        ops.lenet_update(*eng.update_args("step", cursor=None, dbg=dbg, **alone))
 
     def upd_reduce():
-        ops.lenet_update(eng.slab, eng.grid, eng.vslab, B, None, g, *common(), None, None, False, None, 0, None,
-                         eng.mfma)
+        ops.lenet_update(*eng.update_args("reduce", grad=g, with_loss=False, **alone))
 
     def upd_sgd_only():
-        ops.lenet_update(eng.slab, eng.grid, eng.vslab, B, g, None, *common(), None, None, True, None, 0, None,
-                         eng.mfma)
+        ops.lenet_update(*eng.update_args("apply", grad=g, cursor=None))
 
     zbuf = torch.empty(21840, device=dev)
 
@@ -77,15 +72,13 @@ def main():
     for _ in range(3):
         train()
         dbg.zero_()
-        ops.lenet_update(eng.slab, eng.grid, eng.vslab, B, None, None, *common(), None, None, True, eng.loss_parts,
-                         eng.grid, eng.loss_acc, eng.mfma, dbg)
+        upd_full(dbg)
         torch.cuda.synchronize()
     st = dbg.view(256, 8).cpu().double()
     stamps(st, B, "after train")
     for _ in range(3):  # the update again, with nothing in between (its inputs unchanged)
         dbg.zero_()
-        ops.lenet_update(eng.slab, eng.grid, eng.vslab, B, None, None, *common(), None, None, True, eng.loss_parts,
-                         eng.grid, eng.loss_acc, eng.mfma, dbg)
+        upd_full(dbg)
         torch.cuda.synchronize()
     stamps(dbg.view(256, 8).cpu().double(), B, "after update")
 

@@ -27,14 +27,13 @@ def main():
         dt = torch.float16 if B >= 1024 else torch.bfloat16
         eng = FusedLeNetTrainer(Net().to(dev), synthetic_mnist(n, seed=1), global_batch=B, compute_dtype=dt)
         eng.set_epoch_order(torch.randperm(n))
-        nblk = ops.lenet_layout()[-1] if False else 256
+        nblk = 256
         dbg = torch.zeros(nblk * 8, dtype=torch.long, device=dev)
         g = torch.empty(21840, device=dev)
         for _ in range(10):
             eng.gradient()
-            ops.lenet_update(eng.slab, eng.grid, eng.vslab, B, None, g, eng.flat.data, eng.momentum_buf, eng.wimg,
-                             eng.lr, eng.momentum, eng.dampening, eng.weight_decay, eng.nesterov, eng.step_count,
-                             eng.ticket, None, None, False, eng.loss_parts, eng.grid, eng.loss_acc, eng.mfma, dbg)
+            # (the stamped reduce scales nothing and does not take the split-K fc scratch)
+            ops.lenet_update(*eng.update_args("reduce", grad=g, dbg=dbg, scale_in_kernel=True, fc_split=False))
         torch.cuda.synchronize()
         st = dbg.view(nblk, 8).cpu().double()
         live = st[:, 0] > 0
