@@ -47,6 +47,34 @@ def _common_flags(ap: argparse.ArgumentParser) -> None:
                          "(v_mfma_f32_16x16x4_f32, the reference's precision)")
     ap.add_argument("--no-plot", action="store_true")
     ap.add_argument("--out-dir", default=".", help="where images/, results/ and model.pt are written")
+    ap.add_argument("--lr-schedule", choices=["constant", "warmup-cosine", "warmup-step"], default="constant",
+                    help="per-step learning rate, evaluated on the device (optim.LRSchedule) over epochs x steps "
+                         "per epoch: linear warm-up to --lr, then a cosine to --lr-min or --lr-gamma steps "
+                         "(default constant: --lr throughout)")
+    ap.add_argument("--warmup-steps", type=int, default=0, help="optimizer steps of linear warm-up")
+    ap.add_argument("--lr-min", type=float, default=0.0, help="warmup-cosine: the final learning rate")
+    ap.add_argument("--lr-step-size", type=int, default=None,
+                    help="warmup-step: steps between decays (default: one epoch)")
+    ap.add_argument("--lr-gamma", type=float, default=0.1, help="warmup-step: decay factor")
+
+
+def _make_schedule(args, steps_per_epoch: int):
+    """The --lr-schedule flags as an optim.LRSchedule over the whole run (None for ``constant``)."""
+    from ..optim import LRSchedule
+
+    total = max(1, args.epochs * steps_per_epoch)
+    warm = min(max(args.warmup_steps, 0), total - 1)
+    if args.lr_schedule == "warmup-cosine":
+        return LRSchedule.warmup_cosine(args.lr, warm, total, min_lr=args.lr_min)
+    if args.lr_schedule == "warmup-step":
+        return LRSchedule.warmup_step(args.lr, warm, args.lr_step_size or steps_per_epoch, args.lr_gamma, total)
+    return None
+
+
+def _restore_schedule(sched, path: str) -> None:
+    """--resume: the schedule's saved table and position (results/lr_schedule.pth), where there is one."""
+    if sched is not None and os.path.exists(path):
+        sched.load_state_dict(torch.load(path, weights_only=True))
 
 
 def _load_data(args, device):
@@ -96,6 +124,10 @@ def single_main(argv=None) -> int:
     hist.test_counter = [i * n_train for i in range(args.epochs + 1)]
     use_fused = dev.type == "cuda" and args.engine == "fused"
     results = os.path.join(out, "results")
+    sched_path = os.path.join(results, "lr_schedule.pth")
+    sched = _make_schedule(args, (n_train + args.batch_size - 1) // args.batch_size)
+    if args.resume:
+        _restore_schedule(sched, sched_path)
 
     if use_fused:
         from .fused import FusedLeNetTrainer
@@ -107,6 +139,8 @@ def single_main(argv=None) -> int:
             checkpoint.load_checkpoint(net, None, os.path.join(results, "model.pth"), None)
             eng.params_changed()
             eng.load_optimizer_state_dict(torch.load(os.path.join(results, "optimizer.pth"), weights_only=True))
+        if sched is not None:
+            eng.set_lr_schedule(sched)
 
         def test():
             lsum, correct = eng.evaluate(test_set)
@@ -117,6 +151,8 @@ def single_main(argv=None) -> int:
         def save():
             checkpoint.save_model(net, os.path.join(results, "model.pth"))
             checkpoint._atomic_save(opt_state(), os.path.join(results, "optimizer.pth"))
+            if sched is not None:
+                checkpoint._atomic_save(sched.state_dict(), sched_path)
 
         nb = (n_train + args.batch_size - 1) // args.batch_size
         test()
@@ -167,6 +203,8 @@ def single_main(argv=None) -> int:
         if args.resume:
             checkpoint.load_checkpoint(net, tr.opt, os.path.join(results, "model.pth"),
                                        os.path.join(results, "optimizer.pth"))
+        if sched is not None:
+            tr.opt.set_lr_schedule(sched)
         train_loader = DeviceLoader(train, args.batch_size, shuffle=True, device=dev,
                                     dtype=ops.compute_dtype() if dev.type == "cuda" else torch.float32)
         tr.bind_loader(train_loader)
@@ -190,6 +228,8 @@ def single_main(argv=None) -> int:
                 if batch_idx % ckpt_every == 0:
                     checkpoint.save_checkpoint(net, tr.opt, os.path.join(results, "model.pth"),
                                                os.path.join(results, "optimizer.pth"))
+                    if sched is not None:
+                        checkpoint._atomic_save(sched.state_dict(), sched_path)
             test()
 
     if not args.no_plot:
@@ -283,6 +323,9 @@ def dist_main(argv=None) -> int:
 
         eng = FusedLeNetTrainer(net, train, lr=args.lr, momentum=args.momentum, global_batch=args.batch_size,
                                 ctx=ctx, compute_dtype=_dtype(args.dtype), seed=args.seed)
+        sched = _make_schedule(args, -(-len(sampler) // per_rank))
+        if sched is not None:  # (every rank the same table and position: the replicas stay bitwise identical)
+            eng.set_lr_schedule(sched)
         sampler.set_epoch(0)
         order = sampler.indices()
         i = 0
@@ -361,6 +404,9 @@ def dist_main(argv=None) -> int:
                             bucket_cap_mb=25.0 if args.bucket_mb is None else args.bucket_mb)
         loader = DeviceLoader(train, per_rank, sampler=sampler, device=dev,
                               dtype=ops.compute_dtype() if dev.type == "cuda" else torch.float32)
+        sched = _make_schedule(args, len(loader))
+        if sched is not None:
+            tr.opt.set_lr_schedule(sched)
         tr.bind_loader(loader)
         for i in range(args.epochs):
             sampler.set_epoch(i)

@@ -152,7 +152,7 @@ TRAIN_FIELDS = ("images", "labels", "perm", "cursor", "B", "rank", "wimg", "para
 UPDATE_FIELDS = ("slab", "grid", "vslab", "B", "grad_in", "grad_out", "params", "momentum", "wimg", "lr", "mom",
                  "dampening", "weight_decay", "nesterov", "step", "ticket", "cursor", "rng_offset", "apply_sgd",
                  "loss_parts", "nparts", "loss_acc", "mfma_dtype", "dbg", "exch_id", "exch_timeout_s", "grad_post",
-                 "fc_part")
+                 "fc_part", "lr_table", "lr_pos")
 TrainArgs, UpdateArgs = namedtuple("TrainArgs", TRAIN_FIELDS), namedtuple("UpdateArgs", UPDATE_FIELDS)
 _ENGINE = object()  # (default of a builder's ``cursor``: the engine's own device cursor)
 
@@ -259,6 +259,7 @@ class FusedLeNetTrainer:
         self._warmed: set[str] = set()  # step kinds whose capture warm-up has run (see _capture)
         self._cap_stream: torch.cuda.Stream | None = None
         self._stepper: tuple | None = None  # (key, csed.LenetStepper), see stepper()
+        self.lr_schedule = None  # optim.LRSchedule on the device (set_lr_schedule), or None: constant self.lr
         self.native_max = native_max_steps()
         # which training kernel runs a step: 0 auto (the sample-tile kernel, csrc/kernels/
         # lenet_tile.hip, for 16-bit unstaged per-rank batches >= tile_min_batch), 1 the
@@ -680,7 +681,9 @@ class FusedLeNetTrainer:
                     dbg=None, with_loss=True, fc_split=None, scale_in_kernel=None) -> UpdateArgs:
         """The arguments of ``csed::lenet_update`` (UPDATE_FIELDS).  ``mode``: "step" (reduce the slabs, then
         SGD, in one kernel), "reduce" (reduce only, into ``grad``; advances neither cursor nor Philox offset)
-        or "apply" (SGD from the already reduced ``grad``).  The kernel that reduces also sums the loss
+        or "apply" (SGD from the already reduced ``grad``).  The launch that applies SGD ("step" / "apply") gets
+        the learning-rate schedule's table and position where one is set (set_lr_schedule): it trains at
+        its own step's entry and advances the position.  The kernel that reduces also sums the loss
         partials (``with_loss``), applies the 16-bit steps' ``grad_scale`` (train_args), runs the fused
         exchange (``exchange``; default: where the engine has one) and, by default exactly without it, gets
         the split-K fc scratch of per-rank batches > 1024 (``fc_split``)."""
@@ -693,6 +696,7 @@ class FusedLeNetTrainer:
         grad_scale = self.grad_scale if grad_scale is None else grad_scale
         in_kernel = self.fp32 if scale_in_kernel is None else scale_in_kernel
         fc_split = (reduces and exch is None) if fc_split is None else fc_split
+        sch = self.lr_schedule if advances else None
         return UpdateArgs(
             slab=self.slab, grid=grid, vslab=self.vslab, B=B, grad_in=grad if mode == "apply" else None,
             grad_out=grad if mode == "reduce" else None, params=self.flat.data, momentum=self.momentum_buf,
@@ -703,7 +707,8 @@ class FusedLeNetTrainer:
             loss_parts=self.loss_parts if loss else None, nparts=grid if loss else 0,
             loss_acc=self.loss_acc if loss else None, mfma_dtype=self.mfma, dbg=dbg,
             exch_id=-1 if exch is None else exch.id, exch_timeout_s=2.0 if exch is None else self.exch_timeout_s,
-            grad_post=grad_scale if reduces and not in_kernel else 1.0, fc_part=self.fc_part if fc_split else None)
+            grad_post=grad_scale if reduces and not in_kernel else 1.0, fc_part=self.fc_part if fc_split else None,
+            lr_table=None if sch is None else sch.table, lr_pos=None if sch is None else sch.pos)
 
     def _launch_step(self, perm: torch.Tensor, **kw) -> None:
         """A step's launches on ``perm``; ``kw``: B, grid, cursor, grad_scale where not the full step's."""
@@ -773,8 +778,9 @@ class FusedLeNetTrainer:
     # --------------------------------------------------------- graph capture
     def _state(self) -> list[torch.Tensor]:
         """Device tensors a training step advances."""
-        return [self.flat.data, self.momentum_buf, self.wimg, self.step_count, self.cursor, self.rng_offset,
-                self.loss_acc] + ([self.xstage, self.lstage] if self.xstage is not None else [])
+        return ([self.flat.data, self.momentum_buf, self.wimg, self.step_count, self.cursor, self.rng_offset,
+                 self.loss_acc] + ([self.xstage, self.lstage] if self.xstage is not None else [])
+                + ([self.lr_schedule.pos] if self.lr_schedule is not None else []))
 
     def _stamp(self, key: str, dt: float) -> None:
         self.bringup_s[key] = self.bringup_s.get(key, 0.0) + dt
@@ -869,9 +875,15 @@ class FusedLeNetTrainer:
             self._stamp(f"capture.{k}", dt)
         return g
 
+    def _schedule_key(self) -> tuple:
+        """The schedule buffers a captured launch points at (a schedule whose state was reloaded with
+        a table of another length has new ones)."""
+        sch = self.lr_schedule
+        return () if sch is None else (sch.table.data_ptr(), sch.table.numel(), sch.pos.data_ptr())
+
     def graph(self, nsteps: int, tail: bool = False):
         """The captured graph of ``nsteps`` full steps (or of the epoch's tail step), cached."""
-        key = (nsteps, self.perm.data_ptr(), self.perm.numel(), self.B, tail)
+        key = (nsteps, self.perm.data_ptr(), self.perm.numel(), self.B, tail, self._schedule_key())
         if key in self._graphs:
             return self._graphs[key]
         if self.allreduce_kind == "rccl" and dist.is_initialized() and dist.get_backend() == "gloo":
@@ -919,7 +931,8 @@ class FusedLeNetTrainer:
         C++.  None where a step is more than two launches (the all-reduce fallback)."""
         if self.comm and self.exch is None:
             return None
-        key = (self.perm.data_ptr(), -1 if self.exch is None else self.exch.id, self.staged, self.train_kernel)
+        key = (self.perm.data_ptr(), -1 if self.exch is None else self.exch.id, self.staged, self.train_kernel,
+               self._schedule_key())
         if self._stepper is None or self._stepper[0] != key:
             st = torch.classes.csed.LenetStepper()
             st.set_train(*self.train_args(stage_next=True))
@@ -1006,7 +1019,8 @@ class FusedLeNetTrainer:
         if int(self.step_count.item()) > 0 and self.momentum != 0:
             for i in range(len(self.flat.params)):
                 state[i] = {"momentum_buffer": self.flat.view(self.momentum_buf, i).detach().cpu().clone()}
-        group = {"lr": self.lr, "momentum": self.momentum, "dampening": self.dampening,
+        lr = self.lr if self.lr_schedule is None else self.lr_schedule.current_lr()  # (as a torch scheduler leaves it)
+        group = {"lr": lr, "momentum": self.momentum, "dampening": self.dampening,
                  "weight_decay": self.weight_decay, "nesterov": self.nesterov, "maximize": False,
                  "foreach": None, "differentiable": False, "fused": None,
                  "params": list(range(len(self.flat.params)))}
@@ -1025,6 +1039,16 @@ class FusedLeNetTrainer:
         self.lr, self.momentum = float(g["lr"]), float(g["momentum"])
         self._graphs.clear()
         self._stepper = None  # the executor's argument blocks hold lr / momentum
+
+    def set_lr_schedule(self, schedule) -> None:
+        """Train at ``schedule``'s rates (optim.LRSchedule, moved to the engine's device) from its current
+        position on, or at the constant ``self.lr`` again (None).  lenet_update then reads its step's
+        table entry on the device and advances the position: the steps of one graph, or of one
+        native-executor run, train at different rates.  Captured graphs and the executor's argument
+        blocks hold the old rate or table: dropped, as in load_optimizer_state_dict."""
+        self.lr_schedule = None if schedule is None else schedule.to(self.device)
+        self._graphs.clear()
+        self._stepper = None
 
     def params_changed(self) -> None:
         """Call after writing the model parameters from outside (e.g. a checkpoint load)."""

@@ -122,10 +122,14 @@ class ModularTrainer:
         return sloss.clone() if clone_loss else sloss
 
     def _hyper(self) -> tuple:
-        """The optimizer hyper-parameters a captured step bakes into its SGD launch: a change (an LR
-        schedule, manual decay through ``opt.param_groups``) selects a new capture."""
+        """The optimizer hyper-parameters a captured step bakes into its SGD launch: a change (manual
+        decay through ``opt.param_groups``) selects a new capture.  With a device-resident schedule
+        (``opt.set_lr_schedule``) the launch bakes in the schedule's buffers, not a rate: one capture
+        per input shape serves the whole schedule."""
         g = self.opt.param_groups[0]
-        return (float(g["lr"]), float(g["momentum"]), float(g["dampening"]), float(g["weight_decay"]),
+        sch = self.opt.lr_schedule
+        lr = float(g["lr"]) if sch is None else ("schedule", id(sch), sch.table.data_ptr(), sch.pos.data_ptr())
+        return (lr, float(g["momentum"]), float(g["dampening"]), float(g["weight_decay"]),
                 bool(g["nesterov"]), float(self.opt.grad_scale))
 
     def _graph_key(self, x: torch.Tensor, target: torch.Tensor) -> tuple:
@@ -141,7 +145,8 @@ class ModularTrainer:
         loader.into = into
 
     def _state(self) -> list[torch.Tensor]:
-        return [self.flat.data, self.opt.momentum_flat, self.opt.step_count]
+        sch = self.opt.lr_schedule  # (its position: a capture's warm-up step must not advance the schedule)
+        return [self.flat.data, self.opt.momentum_flat, self.opt.step_count] + ([] if sch is None else [sch.pos])
 
     def _capture(self, x: torch.Tensor, target: torch.Tensor):
         """Capture one step at these input shapes into a HIP graph (the engine state advanced by

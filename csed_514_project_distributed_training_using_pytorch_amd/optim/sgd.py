@@ -17,6 +17,7 @@ import torch
 
 from ..ops import _native
 from ..utils.flat import FlatParams
+from .schedule import LRSchedule
 
 
 class FusedSGD(torch.optim.SGD):
@@ -36,6 +37,14 @@ class FusedSGD(torch.optim.SGD):
         self.step_count = torch.zeros(1, dtype=torch.long, device=dev)
         self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self.grad_scale = 1.0
+        self.lr_schedule: LRSchedule | None = None
+
+    def set_lr_schedule(self, schedule: LRSchedule | None) -> None:
+        """Train at ``schedule``'s rates from its current position (moved to the parameters' device) instead
+        of ``param_groups[0]["lr"]``; None returns to the param group's value.  On the GPU the kernel
+        reads the table entry of its step and advances the position itself, so a captured step serves
+        the whole schedule."""
+        self.lr_schedule = None if schedule is None else schedule.to(self.flat.device)
 
     @property
     def on_gpu(self) -> bool:
@@ -54,15 +63,20 @@ class FusedSGD(torch.optim.SGD):
         g = self.param_groups[0]
         self.flat.gather_grads()
         if self.on_gpu:
+            sch = self.lr_schedule
             _native.ops().sgd_flat(self.flat.data, self.flat.grad, self.momentum_flat, float(g["lr"]),
                                    float(g["momentum"]), float(g["dampening"]), float(g["weight_decay"]),
-                                   bool(g["nesterov"]), float(self.grad_scale), self.step_count, self._ticket)
+                                   bool(g["nesterov"]), float(self.grad_scale), self.step_count, self._ticket,
+                                   None if sch is None else sch.table, None if sch is None else sch.pos)
         else:
             self._cpu_step(g)
         return loss
 
     def _cpu_step(self, g) -> None:
         lr, m, damp, wd, nest = g["lr"], g["momentum"], g["dampening"], g["weight_decay"], g["nesterov"]
+        if self.lr_schedule is not None:
+            lr = self.lr_schedule.current_lr()
+            self.lr_schedule.pos += 1
         first = int(self.step_count.item()) == 0
         p, d, buf = self.flat.data, self.flat.grad * self.grad_scale, self.momentum_flat
         if wd:
@@ -82,6 +96,8 @@ class FusedSGD(torch.optim.SGD):
             for i, p in enumerate(self.flat.params):
                 self.state[p]["momentum_buffer"] = self.flat.view(self.momentum_flat, i).detach().clone()
         sd = super().state_dict()
+        if self.lr_schedule is not None:  # (what a torch scheduler leaves in the param group)
+            sd["param_groups"][0]["lr"] = self.lr_schedule.current_lr()
         return sd
 
     def load_state_dict(self, state_dict):

@@ -85,9 +85,24 @@ void gather_normalize(const Tensor& src, const Tensor& idx, const optional<Tenso
 }
 
 // ------------------------------------------------------------- optimizer
+// A device-resident learning-rate schedule's table / position pair (optim/schedule.py), both or neither.
+void check_lr_schedule(const char* op, const Tensor& on, const optional<Tensor>& lr_table,
+                       const optional<Tensor>& lr_pos) {
+  TORCH_CHECK(lr_table.has_value() == lr_pos.has_value(), op, ": lr_table and lr_pos come together");
+  if (!lr_table.has_value()) return;
+  dev(*lr_table, "lr_table"); dev(*lr_pos, "lr_pos");
+  TORCH_CHECK(lr_table->device() == on.device() && lr_pos->device() == on.device(), op,
+              ": lr_table / lr_pos must be on the parameters' device");
+  TORCH_CHECK(lr_table->scalar_type() == at::kFloat && lr_table->is_contiguous(), op, ": lr_table must be float32");
+  TORCH_CHECK(lr_pos->scalar_type() == at::kLong && lr_pos->numel() == 1, op, ": lr_pos must be int64[1]");
+  TORCH_CHECK(lr_table->numel() >= 1 && lr_table->numel() <= INT32_MAX, op, ": lr_table needs at least one entry");
+}
+
 void sgd_flat(Tensor& p, const Tensor& g, Tensor& buf, double lr, double momentum, double dampening,
-              double weight_decay, bool nesterov, double grad_scale, Tensor& step, Tensor& ticket) {
+              double weight_decay, bool nesterov, double grad_scale, Tensor& step, Tensor& ticket,
+              const optional<Tensor>& lr_table, const optional<Tensor>& lr_pos) {
   dev(p, "p"); dev(g, "g"); dev(buf, "buf");
+  check_lr_schedule("sgd_flat", p, lr_table, lr_pos);
   TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat && buf.scalar_type() == at::kFloat);
   TORCH_CHECK(p.numel() == g.numel() && p.numel() == buf.numel());
   TORCH_CHECK(step.scalar_type() == at::kLong && ticket.scalar_type() == at::kInt);
@@ -95,7 +110,8 @@ void sgd_flat(Tensor& p, const Tensor& g, Tensor& buf, double lr, double momentu
   CHECK_HIP(csed::launch_sgd_flat(p.data_ptr<float>(), g.data_ptr<float>(), buf.data_ptr<float>(), p.numel(),
                                   (float)lr, (float)momentum, (float)dampening, (float)weight_decay,
                                   nesterov ? 1 : 0, (float)grad_scale, step.data_ptr<int64_t>(),
-                                  ticket.data_ptr<int>(), cur_stream(p)));
+                                  ticket.data_ptr<int>(), cur_stream(p), optpt<float>(lr_table),
+                                  lr_table.has_value() ? (int)lr_table->numel() : 0, optpt<int64_t>(lr_pos)));
 }
 
 // ---------------------------------------------------------------- softmax
@@ -787,7 +803,8 @@ csed::LenetUpdateArgs update_args(const Tensor& slab, int64_t grid, const Tensor
                                   const optional<Tensor>& cursor, const optional<Tensor>& rng_offset, bool apply_sgd,
                                   const optional<Tensor>& loss_parts, const optional<Tensor>& loss_acc,
                                   int64_t mfma_dtype, const optional<Tensor>& dbg, int64_t exch_id,
-                                  double exch_timeout_s, double grad_post, const optional<Tensor>& fc_part) {
+                                  double exch_timeout_s, double grad_post, const optional<Tensor>& fc_part,
+                                  const optional<Tensor>& lr_table, const optional<Tensor>& lr_pos) {
   dev(slab, "slab"); dev(params, "params"); dev(momentum, "momentum"); dev(wimg, "wimg");
   TORCH_CHECK(params.numel() == csed::lenet_param_count() && momentum.numel() == params.numel(),
               "lenet_update: params / momentum must hold the 21840 flat LeNet parameters");
@@ -819,6 +836,14 @@ csed::LenetUpdateArgs update_args(const Tensor& slab, int64_t grid, const Tensor
   // exch_id >= 0: csrc/comm buffer of the fused gradient exchange (checked by the launcher)
   TORCH_CHECK(exch_id < 0 || !a.grad_in, "lenet_update: the fused exchange reduces the slabs itself (no grad_in)");
   a.exch_id = (int)exch_id; a.exch_timeout_s = exch_timeout_s;
+  // device-resident learning-rate schedule: the kernel that applies SGD picks its step's rate
+  check_lr_schedule("lenet_update", params, lr_table, lr_pos);
+  TORCH_CHECK(apply_sgd || !lr_table.has_value(),
+              "lenet_update: reduce-only mode applies no SGD step and takes no lr_table");
+  if (lr_table.has_value()) {
+    a.lr_table = lr_table->data_ptr<float>(); a.lr_len = (int)lr_table->numel();
+    a.lr_pos = lr_pos->data_ptr<int64_t>();
+  }
   return a;
 }
 
@@ -827,12 +852,13 @@ void lenet_update(const Tensor& slab, int64_t grid, const Tensor& vslab, int64_t
                   double weight_decay, bool nesterov, Tensor& step, Tensor& ticket, const optional<Tensor>& cursor,
                   const optional<Tensor>& rng_offset, bool apply_sgd, const optional<Tensor>& loss_parts,
                   int64_t nparts, const optional<Tensor>& loss_acc, int64_t mfma_dtype, const optional<Tensor>& dbg,
-                  int64_t exch_id, double exch_timeout_s, double grad_post, const optional<Tensor>& fc_part) {
+                  int64_t exch_id, double exch_timeout_s, double grad_post, const optional<Tensor>& fc_part,
+                  const optional<Tensor>& lr_table, const optional<Tensor>& lr_pos) {
   const c10::DeviceGuard gd(params.device());
   const csed::LenetUpdateArgs a =
       update_args(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
                   nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts, loss_acc, mfma_dtype, dbg,
-                  exch_id, exch_timeout_s, grad_post, fc_part);
+                  exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos);
   CHECK_HIP(csed::launch_lenet_update(a, optpt<float>(loss_parts), (int)nparts, optpt<float>(loss_acc),
                                       cur_stream(params)));
 }
@@ -959,18 +985,19 @@ struct LenetStepper : torch::CustomClassHolder {
                   double dampening, double weight_decay, bool nesterov, Tensor step, Tensor ticket,
                   optional<Tensor> cursor, optional<Tensor> rng_offset, bool apply_sgd, optional<Tensor> loss_parts_t,
                   int64_t nparts_, optional<Tensor> loss_acc_t, int64_t mfma_dtype, optional<Tensor> dbg,
-                  int64_t exch_id, double exch_timeout_s, double grad_post, optional<Tensor> fc_part) {
+                  int64_t exch_id, double exch_timeout_s, double grad_post, optional<Tensor> fc_part,
+                  optional<Tensor> lr_table, optional<Tensor> lr_pos) {
     TORCH_CHECK(apply_sgd && !grad_in && !grad_out && cursor, "LenetStepper: set_update takes a full step at a cursor");
     ua = update_args(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
                      nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts_t, loss_acc_t, mfma_dtype, dbg,
-                     exch_id, exch_timeout_s, grad_post, fc_part);
+                     exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos);
     loss_parts = optpt<float>(loss_parts_t);
     loss_acc = optpt<float>(loss_acc_t);
     nparts = nparts_;
     px = {};
     if (exch_id >= 0) CHECK_HIP(csed::comm::ipc_peers((int)exch_id, &px));  // once, not per launch
     keep_u = {slab,   vslab,      params,       momentum,   wimg, step,   ticket,
-              cursor, rng_offset, loss_parts_t, loss_acc_t, dbg,  fc_part};
+              cursor, rng_offset, loss_parts_t, loss_acc_t, dbg,  fc_part, lr_table, lr_pos};
   }
 
   void run(int64_t k) {
@@ -1021,13 +1048,14 @@ TORCH_LIBRARY(csed, m) {
         "bool nesterov, Tensor(e!) step, Tensor(f!) ticket, Tensor(g!)? cursor, Tensor(h!)? rng_offset, "
         "bool apply_sgd, Tensor? loss_parts, int nparts, Tensor(i!)? loss_acc, int mfma_dtype, "
         "Tensor(j!)? dbg=None, int exch_id=-1, float exch_timeout_s=2.0, float grad_post=1.0, "
-        "Tensor(k!)? fc_part=None) -> ()");
+        "Tensor(k!)? fc_part=None, Tensor? lr_table=None, Tensor(l!)? lr_pos=None) -> ()");
   m.def("lenet_eval(Tensor images, Tensor labels, Tensor order, int n, Tensor wimg, Tensor params, float mean, "
         "float std, Tensor(a!) out_parts, Tensor(b!)? logp_out, int mfma_dtype, int kernel=0) -> ()");
   m.def("gather_normalize(Tensor src, Tensor idx, Tensor? cursor, int B, float mean, float std, Tensor(a!) out, "
         "Tensor(b!)? labels_out, Tensor? labels_src) -> ()");
   m.def("sgd_flat(Tensor(a!) p, Tensor g, Tensor(b!) buf, float lr, float momentum, float dampening, "
-        "float weight_decay, bool nesterov, float grad_scale, Tensor(c!) step, Tensor(d!) ticket) -> ()");
+        "float weight_decay, bool nesterov, float grad_scale, Tensor(c!) step, Tensor(d!) ticket, "
+        "Tensor? lr_table=None, Tensor(e!)? lr_pos=None) -> ()");
   m.def("log_softmax_fwd(Tensor x, Tensor(a!) y) -> ()");
   m.def("log_softmax_bwd(Tensor dy, Tensor y, Tensor(a!) dx) -> ()");
   m.def("nll_fwd(Tensor logp, Tensor target, Tensor(a!) out, int reduction, Tensor(b!)? correct) -> ()");

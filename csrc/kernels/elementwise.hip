@@ -53,11 +53,17 @@ hipError_t launch_gather_normalize(const uint8_t* src, const int64_t* idx, const
 //   d = nesterov ? g' + m*buf : buf ;  p -= lr*d
 // The last block to finish bumps step[0] (ticket protocol; every block has
 // read step[0] before it takes its ticket).
+// SCHED: the learning rate is lr_table[min(lr_pos[0], lr_len - 1)] (a device-resident schedule: the
+// host's fp32 values, bit for bit), read by every block before its ticket like step[0]; the block
+// that bumps step[0] advances lr_pos[0].  Its own instantiation: without a table, no extra load.
 // ---------------------------------------------------------------------------
+template <bool SCHED>
 __global__ void sgd_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                 int64_t n, float lr, float m, float damp, float wd, int nesterov,
-                                float gscale, int64_t* step, int* ticket) {
+                                float gscale, int64_t* step, int* ticket, const float* __restrict__ lr_table,
+                                int lr_len, int64_t* lr_pos) {
   const bool first = step[0] == 0;
+  if constexpr (SCHED) lr = lr_table[min(max(lr_pos[0], (int64_t)0), (int64_t)lr_len - 1)];
   const int64_t n4 = n >> 2;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += stride) {
@@ -90,17 +96,24 @@ __global__ void sgd_flat_kernel(float* __restrict__ p, const float* __restrict__
     if (t == (int)gridDim.x - 1) {
       ticket[0] = 0;
       step[0] = step[0] + 1;
+      if constexpr (SCHED) lr_pos[0] = lr_pos[0] + 1;
     }
   }
 }
 
 hipError_t launch_sgd_flat(float* p, const float* g, float* buf, int64_t n, float lr, float momentum,
                            float dampening, float weight_decay, int nesterov, float grad_scale,
-                           int64_t* step, int* ticket, hipStream_t s) {
+                           int64_t* step, int* ticket, hipStream_t s, const float* lr_table, int lr_len,
+                           int64_t* lr_pos) {
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) return hipErrorInvalidValue;
+  if (lr_table && (lr_len < 1 || !lr_pos)) return hipErrorInvalidValue;
   int blocks = (int)std::min<int64_t>(std::max<int64_t>(cdiv(n / 4 + 1, 256), 1), 1024);
-  hipLaunchKernelGGL(sgd_flat_kernel, dim3(blocks), dim3(256), 0, s, p, g, buf, n, lr, momentum,
-                     dampening, weight_decay, nesterov, grad_scale, step, ticket);
+  if (lr_table)
+    hipLaunchKernelGGL(sgd_flat_kernel<true>, dim3(blocks), dim3(256), 0, s, p, g, buf, n, lr, momentum,
+                       dampening, weight_decay, nesterov, grad_scale, step, ticket, lr_table, lr_len, lr_pos);
+  else
+    hipLaunchKernelGGL(sgd_flat_kernel<false>, dim3(blocks), dim3(256), 0, s, p, g, buf, n, lr, momentum,
+                       dampening, weight_decay, nesterov, grad_scale, step, ticket, lr_table, lr_len, lr_pos);
   return hipGetLastError();
 }
 
@@ -506,7 +519,7 @@ hipError_t launch_gate_bwd(const void* dout, int dout_dtype, const void* y, int 
 // lazily, at the TU's first launch): csed::preload_kernels, so a cold epoch does not pay it.
 hipError_t preload_elementwise() {
   hipFuncAttributes attr;
-  return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(sgd_flat_kernel));
+  return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(sgd_flat_kernel<false>));
 }
 
 }  // namespace csed

@@ -1443,10 +1443,11 @@ __global__ void __launch_bounds__(512) lenet_stage_kernel(LenetStageArgs st, con
 
 // Final consumer of one parameter's gradient: export or SGD step.  p / m are
 // params[i] / momentum[i], loaded by the caller at kernel entry so their
-// round trip overlaps the gradient loads instead of following them.
+// round trip overlaps the gradient loads instead of following them.  lr: the launch's learning
+// rate (a.lr, or the caller's entry of the device-resident schedule).
 template <typename T>
 __device__ __forceinline__ void finish_param(const LenetUpdateArgs& a, int i, float gsum, bool first, float p,
-                                             float m, int d0, int d1) {
+                                             float m, int d0, int d1, float lr) {
   if (!a.apply_sgd) {
     a.grad_out[i] = gsum;
     return;
@@ -1459,7 +1460,7 @@ __device__ __forceinline__ void finish_param(const LenetUpdateArgs& a, int i, fl
     a.momentum[i] = bj;
     d = a.nesterov ? fmaf(a.mom, bj, gj) : bj;
   }
-  p = fmaf(-a.lr, d, p);
+  p = fmaf(-lr, d, p);
   a.params[i] = p;
   write_slots<T>(a.wimg, d0, d1, p);
 }
@@ -1469,7 +1470,7 @@ __device__ __forceinline__ void finish_param(const LenetUpdateArgs& a, int i, fl
 // one wide store per array instead of four
 template <typename T>
 __device__ __forceinline__ void finish_param4(const LenetUpdateArgs& a, int i, float4 gsum, bool first, float4 p4,
-                                              float4 m4, int d0) {
+                                              float4 m4, int d0, float lr) {
   float gv[4] = {gsum.x, gsum.y, gsum.z, gsum.w}, pv[4] = {p4.x, p4.y, p4.z, p4.w}, mv[4] = {m4.x, m4.y, m4.z, m4.w};
   if (!a.apply_sgd || a.grad_out) *reinterpret_cast<float4*>(a.grad_out + i) = gsum;
   if (!a.apply_sgd) return;
@@ -1483,7 +1484,7 @@ __device__ __forceinline__ void finish_param4(const LenetUpdateArgs& a, int i, f
       mv[j] = bj;
       d = a.nesterov ? fmaf(a.mom, bj, gj) : bj;
     }
-    pv[j] = fmaf(-a.lr, d, pv[j]);
+    pv[j] = fmaf(-lr, d, pv[j]);
     if constexpr (!std::is_same<T, float>::value) h[j] = h16<T>(pv[j]);
   }
   if (a.mom != 0.f) *reinterpret_cast<float4*>(a.momentum + i) = make_float4(mv[0], mv[1], mv[2], mv[3]);
@@ -1742,8 +1743,10 @@ __device__ __forceinline__ void ll_poll(const comm::IpcPeers& px, const XPtrs<R>
 
 // Update workgroup blk of nblk (UP_NT threads).  part: float4[UP_S][UP_C], part2:
 // float[4][UP_C*4] in LDS.  XW: 0 = no exchange, else the fused exchange's world bound
-// (2, 4 or 8 >= px.world).
-template <typename T, int XW, bool LBC = false>
+// (2, 4 or 8 >= px.world).  SCHED: the learning rate comes from the device-resident schedule
+// (a.lr_table / a.lr_pos) -- its own instantiations, so a launch without a table runs the code it
+// ran before the schedule existed: no load, no barrier, no ticket.
+template <typename T, int XW, bool LBC = false, bool SCHED = false>
 __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ vslab, int B, float* loss_parts,
                             int nparts, float* loss_acc, const comm::IpcPeers& px, uint64_t timeout_ticks, int blk,
                             int nblk, int tid, float4* part_, float* part2_, int fc_tpb, int fc_sl_arg) {
@@ -1785,6 +1788,29 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
     int v = xerr_raw;
     asm volatile("" : "+v"(v));
     return (v & comm::kErrTimeout) != 0;  // (a loopback mismatch is reported, never waited on)
+  };
+  // The scheduled learning rate: position, then table entry -- a dependent pair of loads whose
+  // value only finish_param needs, at the very end.  Both are per-lane loads through opaque(0) like
+  // the tag above.  The position goes out here, first of the block's loads; the table entry
+  // (lr_load) right behind the block's slab / p / m loads, where the only wait in front of it is
+  // for the position (the oldest load in flight: the later ones stay outstanding), so its round
+  // trip overlaps the gradient loads; lr_now passes it through an empty asm where it is consumed.
+  // Every block reads the position before it takes its ticket (below); the last ticket advances it.
+  typedef const __attribute__((address_space(1))) float* gcptrf;
+  const int64_t lrpos_raw = SCHED ? ((gcptr64)a.lr_pos)[opaque(0)] : 0;
+  float lr_raw = 0.f;
+  auto lr_load = [&]() {
+    if constexpr (SCHED)
+      lr_raw = ((gcptrf)a.lr_table)[(int)min(max(lrpos_raw, (int64_t)0), (int64_t)a.lr_len - 1)];
+  };
+  auto lr_now = [&]() {
+    if constexpr (SCHED) {
+      float v = lr_raw;
+      asm volatile("" : "+v"(v));
+      return v;
+    } else {
+      return a.lr;
+    }
   };
   bool timed_out = false;
 #define USTAMP(k) \
@@ -1848,6 +1874,7 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
           if (64 * u < nparts)  // (uniform: only the rounds the grid fills)
             lossv[u] = *reinterpret_cast<const float2*>(loss_parts + 2 * min(tid + 64 * u, nparts - 1));
       }
+      lr_load();
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int u = 0; u < UP_MAXL; ++u)
@@ -1892,7 +1919,7 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
         ll_poll<1, XR, LBC>(px, xp, tag_now(), pbc * (UP_C * 4) + ht, live, g, timeout_ticks, timed_out,
                        a.dbg && tid == 0 && blk < a.dbg_blocks ? a.dbg + blk * 8 : nullptr, blk);
       }
-      finish_param<T>(a, pi, g[0], first, p0, m0, d0, d1);
+      finish_param<T>(a, pi, g[0], first, p0, m0, d0, d1, lr_now());
     }
     USTAMP(4);
     if (pb == 0 && loss_parts && tid < 64) {
@@ -2041,6 +2068,7 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
             }
           };
           ld(0, a0, b0);
+          lr_load();  // (behind the first K group's loads: see below the K loop)
           for (int gi = 0; gi < ng; gi += 2) {
             const bool more = gi + 1 < ng;
             if (more) ld(gi + 1, a1, b1);
@@ -2104,6 +2132,7 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
       constexpr int NC = decltype(nc)::value;
       float a0[NC], b0[NC];
       load_n(nc, k0, a0, b0);
+      lr_load();
       USTAMP(1);
 #pragma unroll
       for (int u = 0; u < NC; ++u) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[u], b0[u], c, 0, 0, 0);
@@ -2117,6 +2146,7 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
     } else if (live_wave && k0 < k1) {
       float a0[16], b0[16], a1[16], b1[16];
       load(k0, a0, b0);
+      lr_load();
       for (int s0 = k0; s0 < k1; s0 += 128) {
         const bool more = s0 + 64 < k1;
         if (more) load(s0 + 64, a1, b1);
@@ -2135,6 +2165,14 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
       }
     }
     }  // fp32 vectors
+    // The schedule's table entry goes out behind the first K group's loads (every slice of a split
+    // tile: any of them may arrive last and finish it).  The p / m prefetch above sits in a divergent
+    // branch, so right behind it hipcc waited for the position with vmcnt(0) -- for the prefetch too,
+    // a round trip in front of the K loop's first loads.  Here the ISA shows a partial wait (vmcnt(12)
+    // / vmcnt(4) in the 4- / 2-step groups of the 16-bit loop) that retires the position and the
+    // prefetch, a round trip old by then, and leaves the K group's loads in flight; the entry's own
+    // round trip overlaps the MFMAs and the combine.  A wave without K-steps (an empty slice) loads it now.
+    if (!(live_wave && k0 < k1)) lr_load();
     USTAMP(2);
     // Retire the p / m prefetch now: after the first finish_param's stores, hipcc would
     // wait for them with vmcnt(0), i.e. for those stores too (one store round trip per
@@ -2242,6 +2280,7 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
         }
       }
       if (do_fin) {
+      const float lr = lr_now();
       if (vec) {
         // MFMA layout (row 4kq + r, column l16) -> row layout through this wave's LDS slot
         float* tr = pfc + wave * 256;
@@ -2251,11 +2290,11 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
         const float4 gv = *reinterpret_cast<const float4*>(tr + (lane >> 2) * 16 + 4 * (lane & 3));
         if (vrow < 50)
           finish_param4<T>(a, vidx, gv, first, make_float4(pp[0], pp[1], pp[2], pp[3]),
-                           make_float4(pm[0], pm[1], pm[2], pm[3]), I_F1 + vrow * LD_F1 + vcol);
+                           make_float4(pm[0], pm[1], pm[2], pm[3]), I_F1 + vrow * LD_F1 + vcol, lr);
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (pidx[r] >= 0) finish_param<T>(a, pidx[r], g[r], first, pp[r], pm[r], fd[r], -1);
+          if (pidx[r] >= 0) finish_param<T>(a, pidx[r], g[r], first, pp[r], pm[r], fd[r], -1, lr);
       }
       }  // do_fin
       USTAMP(4);
@@ -2270,14 +2309,17 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
   if (a.apply_sgd) {
     // Device counters.  cursor / rng_offset are never read by this kernel, so
     // one thread bumps them directly.  step[0] is read by every block only when
-    // dampening != 0; then the last block to take a ticket bumps it.
-    if (a.dampening != 0.f) {
+    // dampening != 0, the schedule's position by every block of a SCHED launch; then the last
+    // block to take a ticket bumps them (bumped by block 0 as soon as it is done, a block that
+    // starts later would read the next step's value).
+    if (SCHED || a.dampening != 0.f) {
       __syncthreads();
       if (tid == 0) {
-        const int t = atomicAdd(a.ticket, 1);  // every block read step[0] before this
+        const int t = atomicAdd(a.ticket, 1);  // every block read step[0] / lr_pos[0] before this
         if (t == nblk - 1) {
           a.ticket[0] = 0;
           if (a.step) a.step[0] += 1;
+          if constexpr (SCHED) a.lr_pos[0] += 1;
         }
       }
     } else if (blk == 0 && tid == 0 && a.step) {
@@ -2295,7 +2337,7 @@ struct UpdateKargs {
   LenetUpdateArgs a; const float* vslab; int B; float* loss_parts; int nparts; float* loss_acc;
   uint64_t timeout_ticks; int fc_tpb; int fc_sl;
 };
-template <typename T, int XW, bool LBC = false>
+template <typename T, int XW, bool LBC = false, bool SCHED = false>
 __global__ void __launch_bounds__(UP_NT) lenet_update_kernel(LenetUpdateArgs a, const float* __restrict__ vslab,
                                                              int B, float* loss_parts, int nparts,
                                                              float* loss_acc, uint64_t timeout_ticks, int fc_tpb,
@@ -2303,27 +2345,31 @@ __global__ void __launch_bounds__(UP_NT) lenet_update_kernel(LenetUpdateArgs a, 
   prefetch_kernargs<sizeof(UpdateKargs) + sizeof(comm::IpcPeers)>();  // (+ gridDim.x after px)
   __shared__ float4 part[UP_S][UP_C];
   __shared__ float part2[4][UP_C * 4];
-  update_role<T, XW, LBC>(a, vslab, B, loss_parts, nparts, loss_acc, px, timeout_ticks, blockIdx.x, gridDim.x,
-                       threadIdx.x, &part[0][0], &part2[0][0], fc_tpb, fc_sl);
+  update_role<T, XW, LBC, SCHED>(a, vslab, B, loss_parts, nparts, loss_acc, px, timeout_ticks, blockIdx.x, gridDim.x,
+                              threadIdx.x, &part[0][0], &part2[0][0], fc_tpb, fc_sl);
 }
 
-// SGD from an already-reduced gradient (DDP: after the all-reduce).
-template <typename T>
+// SGD from an already-reduced gradient (DDP: after the all-reduce).  SCHED: at the schedule's
+// learning rate (see update_role; a uniform load here: nothing is in flight that it could delay).
+template <typename T, bool SCHED = false>
 __global__ void lenet_sgd_kernel(LenetUpdateArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool first = (a.step && a.dampening != 0.f) ? a.step[0] == 0 : false;
+  float lr = a.lr;
+  if constexpr (SCHED) lr = a.lr_table[min(max(a.lr_pos[0], (int64_t)0), (int64_t)a.lr_len - 1)];
   if (i < NP) {
     int d0, d1;
     image_slots(i, d0, d1);
-    finish_param<T>(a, i, a.grad_in[i], first, a.params[i], a.momentum[i], d0, d1);
+    finish_param<T>(a, i, a.grad_in[i], first, a.params[i], a.momentum[i], d0, d1, lr);
   }
-  if (a.dampening != 0.f) {
+  if (SCHED || a.dampening != 0.f) {
     __syncthreads();
     if (threadIdx.x == 0) {
       const int t = atomicAdd(a.ticket, 1);
       if (t == (int)gridDim.x - 1) {
         a.ticket[0] = 0;
         if (a.step) a.step[0] += 1;
+        if constexpr (SCHED) a.lr_pos[0] += 1;
       }
     }
   } else if (i == 0 && a.step) {
@@ -2402,9 +2448,13 @@ static int fc_split_slices(const LenetUpdateArgs& a) {
 
 hipError_t launch_lenet_update(const LenetUpdateArgs& a, float* loss_parts, int nparts, float* loss_acc,
                                hipStream_t s, const comm::IpcPeers* px_cached) {
+  // a device-resident schedule: SGD-applying launches only, with a position and at least one entry
+  const bool sched = a.lr_table != nullptr;
+  if (sched && (!a.apply_sgd || !a.lr_pos || a.lr_len < 1 || !a.ticket)) return hipErrorInvalidValue;
   if (a.apply_sgd && a.grad_in) {
     CSED_DISPATCH_UPDATE(a.mfma_dtype, {
-      hipLaunchKernelGGL(lenet_sgd_kernel<scalar_t>, dim3(cdiv(NP, 256)), dim3(256), 0, s, a);
+      if (sched) hipLaunchKernelGGL((lenet_sgd_kernel<scalar_t, true>), dim3(cdiv(NP, 256)), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((lenet_sgd_kernel<scalar_t, false>), dim3(cdiv(NP, 256)), dim3(256), 0, s, a);
     });
     return hipGetLastError();
   }
@@ -2426,9 +2476,14 @@ hipError_t launch_lenet_update(const LenetUpdateArgs& a, float* loss_parts, int 
     if (px.cap < EXCH_WORDS || a.exch_timeout_s <= 0.0) return hipErrorInvalidValue;
     const uint64_t ticks = (uint64_t)(a.exch_timeout_s * 1e8);  // s_memrealtime: 100 MHz
     // (px.loopback: the looped-back exchange with its invariant check, own instantiations)
-#define CSED_UPDATE_X(W, L)                                                                                   \
-  hipLaunchKernelGGL((lenet_update_kernel<scalar_t, W, L>), dim3(NB_UPDATE), dim3(UP_NT), 0, s, a, a.vslab, a.B, \
+#define CSED_UPDATE_XS(W, L, S)                                                                               \
+  hipLaunchKernelGGL((lenet_update_kernel<scalar_t, W, L, S>), dim3(NB_UPDATE), dim3(UP_NT), 0, s, a, a.vslab, a.B, \
                      loss_parts, nparts, loss_acc, ticks, 1, 1, px)
+#define CSED_UPDATE_X(W, L)                \
+  do {                                     \
+    if (sched) CSED_UPDATE_XS(W, L, true); \
+    else CSED_UPDATE_XS(W, L, false);      \
+  } while (0)
     CSED_DISPATCH_UPDATE(a.mfma_dtype, {
       if (px.loopback) {
         if (px.world <= 2) CSED_UPDATE_X(2, true);
@@ -2441,20 +2496,29 @@ hipError_t launch_lenet_update(const LenetUpdateArgs& a, float* loss_parts, int 
       }
     });
 #undef CSED_UPDATE_X
+#undef CSED_UPDATE_XS
     return hipGetLastError();
   }
   const int S = fc_split_slices(a);
   if (S > 1) {  // split-K fc gradients: one tile per workgroup x S slices (the last one finishes)
     CSED_DISPATCH_UPDATE(a.mfma_dtype, {
-      hipLaunchKernelGGL((lenet_update_kernel<scalar_t, 0>), dim3(FC_TILES * S + NB_CONV), dim3(UP_NT), 0, s, a,
-                         a.vslab, a.B, loss_parts, nparts, loss_acc, (uint64_t)0, 1, S, px);
+      if (sched)
+        hipLaunchKernelGGL((lenet_update_kernel<scalar_t, 0, false, true>), dim3(FC_TILES * S + NB_CONV), dim3(UP_NT),
+                           0, s, a, a.vslab, a.B, loss_parts, nparts, loss_acc, (uint64_t)0, 1, S, px);
+      else
+        hipLaunchKernelGGL((lenet_update_kernel<scalar_t, 0>), dim3(FC_TILES * S + NB_CONV), dim3(UP_NT), 0, s, a,
+                           a.vslab, a.B, loss_parts, nparts, loss_acc, (uint64_t)0, 1, S, px);
     });
     return hipGetLastError();
   }
   const int nblocks = update_blocks(a.B);
   CSED_DISPATCH_UPDATE(a.mfma_dtype, {
-    hipLaunchKernelGGL((lenet_update_kernel<scalar_t, 0>), dim3(nblocks), dim3(UP_NT), 0, s, a, a.vslab,
-                       a.B, loss_parts, nparts, loss_acc, (uint64_t)0, 0, 1, px);
+    if (sched)
+      hipLaunchKernelGGL((lenet_update_kernel<scalar_t, 0, false, true>), dim3(nblocks), dim3(UP_NT), 0, s, a,
+                         a.vslab, a.B, loss_parts, nparts, loss_acc, (uint64_t)0, 0, 1, px);
+    else
+      hipLaunchKernelGGL((lenet_update_kernel<scalar_t, 0>), dim3(nblocks), dim3(UP_NT), 0, s, a, a.vslab,
+                         a.B, loss_parts, nparts, loss_acc, (uint64_t)0, 0, 1, px);
   });
   return hipGetLastError();
 }

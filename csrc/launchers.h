@@ -29,9 +29,12 @@ hipError_t launch_gather_normalize(const uint8_t* src, const int64_t* idx, const
 // SGD with momentum over a flat fp32 buffer (torch.optim.SGD semantics).
 // step[0] == 0 means "momentum buffer not yet initialised" (buf = g).
 // Step counter is bumped by the last block to finish.
+// lr_table (optional, lr_len >= 1 entries) / lr_pos: a device-resident schedule -- the launch trains at
+// lr_table[min(lr_pos[0], lr_len - 1)] instead of lr and the block that bumps step[0] advances lr_pos[0].
 hipError_t launch_sgd_flat(float* p, const float* g, float* buf, int64_t n, float lr, float momentum,
                            float dampening, float weight_decay, int nesterov, float grad_scale,
-                           int64_t* step, int* ticket, hipStream_t s);
+                           int64_t* step, int* ticket, hipStream_t s, const float* lr_table = nullptr,
+                           int lr_len = 0, int64_t* lr_pos = nullptr);
 
 // ------------------------------------------------------------- softmax ----
 // log_softmax over the last dim of x[rows, C] (any float dtype in, fp32 out).
@@ -285,6 +288,11 @@ struct LenetUpdateArgs {
   // before SGD / export.  The buffer needs lenet_exch_words() words per sender.
   int exch_id;
   double exch_timeout_s;
+  // Device-resident learning-rate schedule (optional; apply_sgd only): with lr_table set the launch
+  // trains at lr_table[min(lr_pos[0], lr_len - 1)] instead of lr, every block reading lr_pos[0] at its
+  // entry, and the last block to take a ticket advances lr_pos[0] (once per SGD-applying launch).
+  // lr_pos is the schedule's own counter: step[0] only encodes "momentum buffer exists".
+  const float* lr_table; int lr_len; int64_t* lr_pos;
 };
 int64_t lenet_exch_words();
 // loss_parts [nparts, 2] are summed in a fixed order into loss_acc[2] (optional).
