@@ -1295,10 +1295,21 @@ __device__ __forceinline__ void image_slots_flat(int i, int& d0, int& d1) {
 
 // (T = float: the fp32 path, lenet_fused_f32.hip, reads the fp32 master parameters and
 // keeps no weight images)
+// A weight-image element is the 16-bit rounding of the fp32 master parameter AS STORED: what
+// lenet_pack makes of it.  For fp16, hipcc otherwise folds the convert into the SGD step's fma
+// (v_fma_mixlo_f16: the exact fma result rounded once, to fp16), and where the fp32 rounding lands on
+// an fp16 tie the image is one ulp off the repacked one.  The empty asm ends the fold: the convert
+// reads the fp32 register.  (bf16 has no such instruction; its code is unchanged.)
+template <typename T>
+__device__ __forceinline__ float as_stored(float v) {
+  if constexpr (!std::is_same<T, float>::value && !std::is_same<T, __bf16>::value) asm volatile("" : "+v"(v));
+  return v;
+}
+
 template <typename T>
 __device__ __forceinline__ void write_slots(unsigned short* wimg, int d0, int d1, float v) {
   if constexpr (!std::is_same<T, float>::value) {
-    const unsigned short h = h16<T>(v);
+    const unsigned short h = h16<T>(as_stored<T>(v));
     if (d0 >= 0) wimg[d0] = h;
     if (d1 >= 0) wimg[d1] = h;
   }
@@ -1485,7 +1496,7 @@ __device__ __forceinline__ void finish_param4(const LenetUpdateArgs& a, int i, f
       d = a.nesterov ? fmaf(a.mom, bj, gj) : bj;
     }
     pv[j] = fmaf(-lr, d, pv[j]);
-    if constexpr (!std::is_same<T, float>::value) h[j] = h16<T>(pv[j]);
+    if constexpr (!std::is_same<T, float>::value) h[j] = h16<T>(as_stored<T>(pv[j]));
   }
   if (a.mom != 0.f) *reinterpret_cast<float4*>(a.momentum + i) = make_float4(mv[0], mv[1], mv[2], mv[3]);
   *reinterpret_cast<float4*>(a.params + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);

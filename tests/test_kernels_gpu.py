@@ -193,6 +193,7 @@ def test_log_softmax_nll():
 
 
 def test_sgd_flat_matches_torch():
+    # (lr + momentum only; test_update_oracle_gpu.py runs dampening, weight decay, Nesterov and momentum 0)
     torch.manual_seed(6)
     n = 21840
     p0 = torch.randn(n)
