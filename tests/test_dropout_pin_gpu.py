@@ -15,7 +15,9 @@ lenet_fused_f32.hip stage 0).  Bit parity with torch's CPU generator is impossib
 * with the host-regenerated masks applied in the CPU fp32 ``Net``, the exact-fp32 kernel's
   gradients match to 1e-4 relative L2 for every parameter at p = 0.5.
 """
-import numpy as np
+import os
+import sys
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -24,19 +26,13 @@ from csed_514_project_distributed_training_using_pytorch_amd.data import synthet
 from csed_514_project_distributed_training_using_pytorch_amd.data.mnist import MNIST_MEAN, MNIST_STD
 from csed_514_project_distributed_training_using_pytorch_amd.engine.fused import FusedLeNetTrainer
 from csed_514_project_distributed_training_using_pytorch_amd.models import Net
-from csed_514_project_distributed_training_using_pytorch_amd.ops.rng import philox_uniform_reference
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _lenet_oracle import host_masks  # noqa: E402  (the host Philox keep masks, shared with the per-sample oracle)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
 V_P2, V_H = 0, 384  # per-sample vector slab: fc1 input (after Dropout2d) | fc1 output (after dropout)
-
-
-def host_masks(seed, counter, rank, B, p):
-    """Keep masks of one step as the kernels draw them: [B, 20] Dropout2d channels, [B, 50] units."""
-    e = (np.arange(B, dtype=np.uint64)[:, None] + np.uint64(rank * B)) * np.uint64(70) + np.arange(70, dtype=np.uint64)
-    u = philox_uniform_reference(seed, counter << 20, e)
-    keep = u >= np.float32(p)
-    return torch.from_numpy(keep[:, :20].copy()), torch.from_numpy(keep[:, 20:].copy())
 
 
 def _positive_net():

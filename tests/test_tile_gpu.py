@@ -7,6 +7,10 @@ images, same K orders and accumulation chains, same Philox dropout draws), so th
 accuracy and the fc gradients (formed by lenet_update from the per-sample vectors) must match
 bit for bit; the conv gradients sum in another order and must match to fp32 rounding of
 16-bit products.
+
+These are comparisons between HIP kernels, and bands against the fp32 reference.  The tight check of
+this kernel against a reference of its own is tests/test_lenet_oracle_gpu.py (test_tile_kernel: short
+last tiles, per slab row, against the rounding-matched fp64 oracle of each sample).
 """
 import pytest
 import torch
