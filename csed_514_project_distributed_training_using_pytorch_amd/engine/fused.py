@@ -53,9 +53,6 @@ from ..parallel import ipc as _ipc
 from ..parallel.ipc import allreduce_mode, open_exchange, open_loopback_exchange, wait_timeout_s
 from ..utils.flat import FlatParams
 
-N_VEC = 464  # per-sample fc vector length (kernels/lenet_layout.h VEC)
-
-
 _HIP_LIBS: list | None = None
 
 
@@ -129,6 +126,7 @@ class LenetLayout(NamedTuple):
     split_k: int  # workgroups per sample of the split step (csed::lenet_train KS)
     tile_samples: int  # samples per tile of the sample-tile training kernel (csrc/kernels/lenet_tile.hip)
     tile_min_batch: int  # smallest per-rank batch the auto mode runs on the sample-tile kernel
+    fc_part_elems: int  # floats of lenet_update's split-K fc scratch (partial sums, then the tiles' arrival counters)
 
 
 @functools.lru_cache(maxsize=None)
@@ -139,9 +137,51 @@ def lenet_layout() -> LenetLayout:
     return lay
 
 
+PER_SAMPLE, TILE, FP32 = 0, 1, 2  # LenetPlan.kernel
+STRIDED, STAGED, SPLIT = 0, 1, 2  # LenetPlan.variant
+KERNEL_NAMES = ("lenet_train", "lenet_tile", "lenet_train_f32")
+
+
+class LenetPlan(NamedTuple):
+    """What one ``csed::lenet_train`` / ``lenet_eval`` launch runs: ``csed::lenet_plan``'s values, in its order
+    (csrc/kernels/lenet_plan.h, the rule the launchers themselves dispatch on)."""
+    kernel: int  # PER_SAMPLE, TILE or FP32
+    variant: int  # STRIDED over samples (tiles), one STAGED sample per workgroup, or the SPLIT step
+    grid: int
+    one_tile: int  # tile kernel: every workgroup has exactly one tile
+    stage_rows: int  # staging rows the launch reads and writes (0: it gathers through perm)
+    error: str  # "" for a valid launch, else the rule it breaks
+
+
+class LenetGeometry(NamedTuple):
+    """The engine's default full step at a per-rank batch: ``csed::lenet_geometry``'s values, in its order."""
+    grid: int
+    split: int  # the split step (split_k workgroups per sample)
+    staged: int  # a staged batch of one row per workgroup
+    tile_staged: int  # the tile kernel, staging every workgroup's first tile
+    stage_rows: int
+
+
+@functools.lru_cache(maxsize=None)
+def lenet_plan(B: int, grid: int, mfma: int, kernel: int = 0, staged: bool = False, stage_next: bool = False,
+               cursor: bool = True, train: bool = True) -> LenetPlan:
+    """The plan of a launch (``kernel``: the request, 0 auto / 1 per sample / 2 tile).  No GPU needed."""
+    _native.require()
+    values, error = torch.ops.csed.lenet_plan(B, grid, mfma, kernel, staged, stage_next, cursor, train)
+    return LenetPlan(*(int(v) for v in values), error)
+
+
+def lenet_geometry(B: int, mfma: int, grid: int = 0, allow_split: bool = True) -> LenetGeometry:
+    """The default geometry at per-rank batch B (``grid`` 0: min(B, 256)).  No GPU needed."""
+    _native.require()
+    return LenetGeometry(*(int(v) for v in torch.ops.csed.lenet_geometry(B, mfma, grid, allow_split)))
+
+
+@functools.lru_cache(maxsize=None)
 def tile_grid(B: int) -> int:
     """Workgroups of the sample-tile kernel at per-rank batch B."""
-    return min(256, -(-B // lenet_layout().tile_samples))
+    _native.require()
+    return int(torch.ops.csed.lenet_tile_grid(B))
 
 
 # Argument names of a step's two launches in the order of their op schemas (csrc/bindings.cpp; LenetStepper's
@@ -193,24 +233,21 @@ class FusedLeNetTrainer:
             raise ValueError(f"compute dtype {compute_dtype}: expected bfloat16, float16 or float32")
         lay = lenet_layout()
         self.fp32 = compute_dtype == torch.float32
-        # batch staging (per-rank batch <= stage_max_batch, one workgroup per sample): lenet_update
-        # gathers the next step's pixels + labels one step ahead, so lenet_train starts with no
-        # dependent index chain.  Split step (lenet_fused.hip / lenet_fused_f32.hip KS > 1): split_k
-        # workgroups per sample share the backward conv stages; used whenever the whole grid fits
-        # one wave of the GPU (split_k * B <= 256 CUs).  CSED_SPLIT=0 keeps one workgroup per
-        # sample.  The exact-fp32 kernel gathers its samples itself and stages its batch only in
-        # the split step.
-        self.grid = int(grid) if grid else min(self.B, 256)
+        self.mfma = _native.MFMA_CODE[compute_dtype]
+        # The step's geometry (csrc/kernels/lenet_plan.h lenet_geometry).  Batch staging (one workgroup
+        # per sample): lenet_update gathers the next step's pixels + labels one step ahead, so lenet_train
+        # starts with no dependent index chain.  Split step (lenet_fused.hip / lenet_fused_f32.hip KS > 1):
+        # split_k workgroups per sample share the backward conv stages; used whenever the whole grid fits
+        # one wave of the GPU.  CSED_SPLIT=0 keeps one workgroup per sample.  The exact-fp32 kernel gathers
+        # its samples itself and stages its batch only in the split step.  The sample-tile kernel (16-bit
+        # large batches, csrc/kernels/lenet_tile.hip) stages the first tile of every workgroup instead.
         auto = os.environ.get("CSED_SPLIT", "auto").strip().lower() != "0"
-        can_stage = self.B <= lay.stage_max_batch and self.grid == self.B
-        self.split = (can_stage and grid is None and lay.split_k * self.B <= 256
-                      and (auto if split is None else bool(split)))
-        self.staged = can_stage and (not self.fp32 or self.split)
-        if self.split:
-            self.grid = lay.split_k * self.B
+        geo = lenet_geometry(self.B, self.mfma, int(grid) if grid else 0,
+                             grid is None and (auto if split is None else bool(split)))
+        self.grid, self.split, self.staged = geo.grid, bool(geo.split), bool(geo.staged)
+        self.tile_staged = bool(geo.tile_staged)
         self.lr, self.momentum, self.dampening = float(lr), float(momentum), float(dampening)
         self.weight_decay, self.nesterov = float(weight_decay), bool(nesterov)
-        self.mfma = _native.MFMA_CODE[compute_dtype]
         self.compute_dtype = compute_dtype
         self.drop_p = float(drop_p)
         self.seed = int(seed)  # masks decorrelate across ranks through the rank id in the element index
@@ -243,13 +280,11 @@ class FusedLeNetTrainer:
         # without the fused exchange form the fc weight gradients as up to 8 batch slices per
         # tile on all CUs, the tile's last slice finishing it (8 x 88 tiles x 256 partial sums,
         # then 88 arrival counters that must start at zero)
-        self.fc_part = _native.zeros(8 * 88 * 256 + 128, torch.float32, dev) if self.B > 1024 else None
-        # one staging row per workgroup (split step: row r holds sample r % B)
-        # the sample-tile kernel (16-bit, per-rank batch >= tile_min_batch) stages the first tile
-        # of every workgroup instead: grid * tile_samples rows (csrc/kernels/lenet_tile.hip)
-        self.tile_staged = (not self.fp32 and not self.staged and self.B >= lay.tile_min_batch
-                            and self.grid == tile_grid(self.B))
-        srows = self.grid if self.staged else (self.grid * lay.tile_samples if self.tile_staged else 0)
+        self.fc_part = (_native.zeros((lay.fc_part_elems + 127) // 128 * 128, torch.float32, dev) if self.B > 1024
+                        else None)
+        # one staging row per workgroup (split step: row r holds sample r % B), or the tile kernel's
+        # grid * tile_samples rows
+        srows = geo.stage_rows
         self.xstage = _native.zeros((srows, 784), torch.uint8, dev) if srows else None
         self.lstage = _native.zeros(srows, torch.long, dev) if srows else None
         t_mark = time.perf_counter()
@@ -261,9 +296,8 @@ class FusedLeNetTrainer:
         self._stepper: tuple | None = None  # (key, csed.LenetStepper), see stepper()
         self.lr_schedule = None  # optim.LRSchedule on the device (set_lr_schedule), or None: constant self.lr
         self.native_max = native_max_steps()
-        # which training kernel runs a step: 0 auto (the sample-tile kernel, csrc/kernels/
-        # lenet_tile.hip, for 16-bit unstaged per-rank batches >= tile_min_batch), 1 the
-        # per-sample lenet_train, 2 the sample-tile kernel
+        # which training kernel a step asks for: 0 auto (the sample-tile kernel, csrc/kernels/lenet_tile.hip,
+        # for large 16-bit per-rank batches), 1 the per-sample lenet_train, 2 the sample-tile kernel
         self.train_kernel = 0
         self._eval_cache: dict[int, tuple] = {}
         self._order_host: torch.Tensor | None = None
@@ -318,8 +352,8 @@ class FusedLeNetTrainer:
     def _vec16(self, B: int) -> torch.Tensor:
         """The 16-bit kernels' fc-vector slab of a batch of B: raw [round_up(B, 64) / 4, 464, 4]
         (sample quads, kernels/lenet_layout.h)."""
-        q = (B + 63) // 64 * 16
-        return self.vslab.view(-1).view(torch.int16)[:q * N_VEC * 4].view(q, N_VEC, 4)
+        q, nv = (B + 63) // 64 * 16, lenet_layout().vec_len
+        return self.vslab.view(-1).view(torch.int16)[:q * nv * 4].view(q, nv, 4)
 
     def fc_vectors(self, B: int | None = None) -> torch.Tensor:
         """The step's per-sample fc vectors (P2 | dZ1 | H | dlogits) as fp32 [B, 464], decoded
@@ -327,7 +361,7 @@ class FusedLeNetTrainer:
         B = self.B if B is None else int(B)
         if self.fp32:
             return self.vslab[:B].clone()
-        v = self._vec16(B).transpose(1, 2).reshape(-1, N_VEC)[:B]  # [quad, 4, 464] -> [sample, 464]
+        v = self._vec16(B).transpose(1, 2).reshape(-1, lenet_layout().vec_len)[:B]  # [quad, 4, 464] -> [sample, 464]
         return v.contiguous().view(self.compute_dtype).float()
 
     def set_fc_vectors(self, v: torch.Tensor) -> None:
@@ -337,9 +371,10 @@ class FusedLeNetTrainer:
         if self.fp32:
             self.vslab[:B].copy_(v)
             return
-        buf = torch.zeros(((B + 63) // 64 * 64, N_VEC), dtype=self.compute_dtype, device=self.device)
+        nv = lenet_layout().vec_len
+        buf = torch.zeros(((B + 63) // 64 * 64, nv), dtype=self.compute_dtype, device=self.device)
         buf[:B] = v.to(device=self.device, dtype=self.compute_dtype)
-        self._vec16(B).copy_(buf.view(torch.int16).view(-1, 4, N_VEC).transpose(1, 2))
+        self._vec16(B).copy_(buf.view(torch.int16).view(-1, 4, nv).transpose(1, 2))
 
     @property
     def allreduce_kind(self) -> str:
@@ -624,21 +659,18 @@ class FusedLeNetTrainer:
 
     def uses_tile_kernel(self, B: int | None = None, grid: int | None = None) -> bool:
         """Whether a full step of per-rank batch B on ``grid`` workgroups runs the sample-tile kernel
-        (csrc/kernels/lenet_tile.hip) -- the launcher's own rule (bindings.cpp lenet_train) for
-        kernel_for()'s choice: 16-bit, and kernel 2, or kernel 0 (auto) with B >= tile_min_batch."""
-        B = self.B if B is None else B
-        grid = self.grid if grid is None else grid
-        if self.fp32:
-            return False
-        k = self.kernel_for(B, grid)
-        return k == 2 or (k == 0 and B >= lenet_layout().tile_min_batch)
+        (csrc/kernels/lenet_tile.hip): the plan of kernel_for()'s request."""
+        return self._plan(B, grid).kernel == TILE
+
+    def _plan(self, B: int | None = None, grid: int | None = None, staged: bool = False) -> LenetPlan:
+        """The plan of this engine's training launch of per-rank batch B on ``grid`` workgroups."""
+        B, grid = self.B if B is None else B, self.grid if grid is None else grid
+        return lenet_plan(B, grid, self.mfma, self.kernel_for(B, grid), staged)
 
     @property
     def kernel_names(self) -> str:
         """The HIP kernels of one full training step, as launched (reports)."""
-        if self.fp32:
-            return "lenet_train_f32 + lenet_update"
-        return ("lenet_tile" if self.uses_tile_kernel() else "lenet_train") + " + lenet_update"
+        return KERNEL_NAMES[self._plan().kernel] + " + lenet_update"
 
     @property
     def step_kind(self) -> str:
@@ -724,14 +756,16 @@ class FusedLeNetTrainer:
 
     def _stages(self, kernel: int) -> bool:
         """Whether a full step launched with ``kernel`` (kernel_for) reads / writes the staging
-        buffers: the per-sample kernel's (one row per workgroup) or the tile kernel's (first tiles)."""
-        if self.staged:
-            return kernel != 2
-        return self.tile_staged and kernel != 1
+        buffers: the per-sample kernel's (one row per workgroup) or the tile kernel's (first tiles) --
+        where the engine stages at all, a launch whose plan takes exactly the rows it keeps."""
+        if not (self.staged or self.tile_staged):
+            return False
+        p = lenet_plan(self.B, self.grid, self.mfma, kernel, True)
+        return not p.error and p.stage_rows == self.xstage.shape[0]
 
     def kernel_for(self, B: int, grid: int) -> int:
         """``train_kernel`` for a launch of per-rank batch B on ``grid`` workgroups: the tile kernel
-        only where its grid (min(256, ceil(B / tile_samples))) is the launch's, else per-sample."""
+        only where its grid (tile_grid) is the launch's, else per-sample."""
         if self.train_kernel == 0:
             return 0 if (B < lenet_layout().tile_min_batch or grid == tile_grid(B)) else 1
         if self.train_kernel == 2 and grid != tile_grid(B):

@@ -22,6 +22,7 @@ Reference parity map (ref = /root/reference):
 """
 from __future__ import annotations
 
+import functools
 import os
 
 import torch
@@ -143,11 +144,13 @@ def release_grad_buffers(params) -> None:
             _handed_out.discard(id(p))
 
 
+@functools.lru_cache(maxsize=None)
 def wgrad_workspace_elems(N: int, IC: int, KH: int, KW: int, OC: int) -> int:
-    """Floats of a conv weight-gradient workspace: one [OC, IC*KH*KW + 1] partial slab per block,
-    sized for the most blocks csrc/kernels/conv.hip conv2d_wgrad_blocks makes (256, 512 from
-    N = 2048; the extension checks the size)."""
-    return max(1, min(N, 512 if N >= 2048 else 256)) * OC * (IC * KH * KW + 1)
+    """Floats of a conv weight-gradient workspace: one [OC, IC*KH*KW + 1] partial slab per block the
+    kernel runs for a batch of N (csrc/kernels/conv.hip conv2d_wgrad_blocks, at most 256) -- the
+    extension's own ``csed::conv2d_wgrad_workspace``, the size its ops check."""
+    _native.require()
+    return int(torch.ops.csed.conv2d_wgrad_workspace(N, IC, KH, KW, OC))
 
 
 # The deferred weight-gradient slab reduce.  A conv backward normally ends with its own reduce

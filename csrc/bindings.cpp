@@ -612,11 +612,27 @@ void wgrad_reduce(const Tensor& ws, Tensor& dw, const optional<Tensor>& db, int6
 // Buffer sizes the fused LeNet kernels expect: [weight-image elements, conv slab row (floats per
 // workgroup), per-sample vector length, flat params, largest per-rank batch the batch-staging path
 // handles, exchange words per sender, workgroups per sample of the split step, samples per tile of
-// the sample-tile kernel, smallest per-rank batch the auto mode runs on it] (engine/fused.py LenetLayout).
+// the sample-tile kernel, smallest per-rank batch the auto mode runs on it, floats of lenet_update's split-K
+// fc scratch] (engine/fused.py LenetLayout).
 std::vector<int64_t> lenet_layout() {
   return {csed::lenet_wimg_elems(), csed::lenet_conv_param_count(), csed::lenet_vec_len(),
-          csed::lenet_param_count(), csed::lenet_stage_max_batch(), csed::lenet_exch_words(),
-          csed::lenet_split_k(), csed::lenet_tile_samples(), csed::lenet_tile_min_batch()};
+          csed::lenet_param_count(), csed::kLenetStageMaxB, csed::lenet_exch_words(),
+          csed::lenet::SPLIT_K, csed::kLenetTileSamples, csed::kLenetTileMinB, csed::lenet_fc_part_elems()};
+}
+
+// kernels/lenet_plan.h for Python (engine/fused.py LenetPlan / LenetGeometry; integers only, so no GPU):
+// a launch's [kernel, variant, grid, one_tile, stage_rows] and the rule it breaks ("" for a valid one)
+std::tuple<std::vector<int64_t>, std::string> lenet_plan(int64_t B, int64_t grid, int64_t mfma_dtype, int64_t kernel,
+                                                         bool staged, bool stage_next, bool cursor, bool train) {
+  const csed::LenetPlan p = csed::lenet_plan((int)B, (int)grid, lcode(mfma_dtype), (int)kernel, staged, staged,
+                                             stage_next, cursor, train);
+  return {{p.kernel, p.variant, p.grid, p.one_tile, p.stage_rows}, p.error ? p.error : ""};
+}
+
+// the engine's default step: [grid, split, staged, tile_staged, stage_rows]
+std::vector<int64_t> lenet_geometry(int64_t B, int64_t mfma_dtype, int64_t grid, bool allow_split) {
+  const csed::LenetGeometry g = csed::lenet_geometry((int)B, lcode(mfma_dtype), (int)grid, allow_split);
+  return {g.grid, g.split, g.staged, g.tile_staged, g.stage_rows};
 }
 
 // Load the code objects of the kernel translation units named by `mask` on `device` now, from
@@ -702,16 +718,12 @@ csed::LenetTrainArgs train_args(const Tensor& images, const Tensor& labels, cons
   dev(slab, "slab"); dev(vslab, "vslab"); dev(loss_parts, "loss_parts");
   TORCH_CHECK(images.scalar_type() == at::kByte && images.numel() == images.size(0) * 784, "images: uint8 [N,28,28]");
   TORCH_CHECK(labels.scalar_type() == at::kLong && perm.scalar_type() == at::kLong);
-  TORCH_CHECK(grid >= 1 && (grid <= B || (xstage.has_value() && grid == csed::lenet_split_k() * B)) && grid <= 1024,
-              "lenet_train: 1 <= grid <= B (or split_k * B for a staged batch)");
-  TORCH_CHECK(kernel >= 0 && kernel <= 2, "lenet_train: kernel 0 (auto), 1 (per sample) or 2 (sample tiles)");
-  const bool tile = mfma_dtype != csed::kF32 && (kernel == 2 || (kernel == 0 && B >= csed::kLenetTileMinB));
-  if (tile)
-    TORCH_CHECK(grid == csed::lenet_tile_grid((int)B), "lenet_train: the sample-tile kernel runs grid ",
-                csed::lenet_tile_grid((int)B));
-  // staging rows: the tile kernel stages every workgroup's first tile, the per-sample kernel one
-  // sample per workgroup
-  const int64_t srows = tile ? grid * csed::lenet_tile_samples() : grid;
+  // which kernel, on a valid grid, with how many staging rows (stage_next counts for a staged batch only)
+  const csed::LenetPlan plan =
+      csed::lenet_plan((int)B, (int)grid, lcode(mfma_dtype), (int)kernel, xstage.has_value(), lstage.has_value(),
+                       stage_next && xstage.has_value(), cursor.has_value(), true);
+  TORCH_CHECK(!plan.error, "lenet_train: ", plan.error);
+  const int64_t srows = plan.stage_rows;
   TORCH_CHECK(slab.numel() >= grid * csed::lenet_conv_param_count() && loss_parts.numel() >= 2 * grid,
               "lenet_train: slab [grid, 5280] / loss_parts [grid, 2] too small");
   TORCH_CHECK(vslab.scalar_type() == at::kFloat && vslab.numel() * 4 >= vec_bytes(B, mfma_dtype),
@@ -725,29 +737,20 @@ csed::LenetTrainArgs train_args(const Tensor& images, const Tensor& labels, cons
   a.vslab = vslab.data_ptr<float>(); a.loss_acc = loss_parts.data_ptr<float>(); a.grad_scale = (float)grad_scale; a.mean = (float)mean;
   a.std_ = (float)std_; a.drop_p = (float)drop_p; a.seed = (uint64_t)seed; a.rng_offset = optpt<int64_t>(rng_offset);
   a.grid = (int)grid; a.mfma_dtype = lcode(mfma_dtype); a.kernel = (int)kernel;
-  if (a.mfma_dtype == csed::kF32)
-    TORCH_CHECK(grid <= 256 && (!xstage.has_value() || grid == csed::lenet_split_k() * B),
-                "lenet_train fp32: grid <= 256; a staged batch runs the split step (grid = split_k * B)");
   if (dbg.has_value()) {
     TORCH_CHECK(dbg->scalar_type() == at::kLong && dbg->numel() >= 32 * grid, "dbg: int64 [grid*32]");
     a.dbg = (uint64_t*)dbg->data_ptr<int64_t>();
     // a buffer of >= 48 x grid words also takes every wave's entry stamp (after the 32 x grid)
     if (dbg->numel() >= 48 * grid) a.dbg_entry = a.dbg + 32 * grid;
   }
-  TORCH_CHECK(xstage.has_value() == lstage.has_value(), "lenet_train: xstage and lstage go together");
   if (xstage.has_value()) {
     TORCH_CHECK(xstage->scalar_type() == at::kByte && xstage->numel() >= srows * 784 && lstage->scalar_type() == at::kLong &&
                     lstage->numel() >= srows && xstage->is_contiguous() && lstage->is_contiguous(),
                 "lenet_train: staged batch must be uint8 [rows, 784] + int64 [rows] (rows: one per workgroup; "
                 "the sample-tile kernel: one per sample of every workgroup's first tile)");
-    TORCH_CHECK(tile || grid == B || grid == csed::lenet_split_k() * B,
-                "lenet_train: the per-sample kernel stages one sample per workgroup (grid == B or split_k * B)");
     a.xstage = xstage->data_ptr<uint8_t>();
     a.lstage = lstage->data_ptr<int64_t>();
-    if (stage_next) {
-      TORCH_CHECK(cursor.has_value(), "lenet_train: stage_next needs the cursor");
-      a.stage_next = 1;
-    }
+    a.stage_next = stage_next ? 1 : 0;
   }
   return a;
 }
@@ -783,8 +786,8 @@ csed::LenetStageArgs stage_args(const Tensor& images, const Tensor& labels, cons
   st.xstage = xstage.data_ptr<uint8_t>(); st.lstage = lstage.data_ptr<int64_t>();
   // one staging row per workgroup: B, or split_k * B for the split step (row r = sample r % B)
   st.rows = (int)lstage.numel();
-  TORCH_CHECK(st.rows >= 1 && st.rows <= csed::lenet_stage_max_batch() && xstage.numel() >= (int64_t)st.rows * 784,
-              "staging: 1..", csed::lenet_stage_max_batch(), " rows (lstage) with xstage [rows, 784]");
+  TORCH_CHECK(st.rows >= 1 && st.rows <= csed::kLenetStageMaxB && xstage.numel() >= (int64_t)st.rows * 784,
+              "staging: 1..", csed::kLenetStageMaxB, " rows (lstage) with xstage [rows, 784]");
   return st;
 }
 
@@ -866,10 +869,14 @@ void lenet_update(const Tensor& slab, int64_t grid, const Tensor& vslab, int64_t
 void lenet_eval(const Tensor& images, const Tensor& labels, const Tensor& order, int64_t n, const Tensor& wimg,
                 const Tensor& params, double mean, double std_, Tensor& out_parts, const optional<Tensor>& logp_out,
                 int64_t mfma_dtype, int64_t kernel) {
-  TORCH_CHECK(kernel >= 0 && kernel <= 2, "lenet_eval: kernel 0 (auto), 1 (per sample) or 2 (sample tiles)");
-  TORCH_CHECK(kernel != 2 || out_parts.numel() >= 2 * csed::lenet_tile_grid((int)n), "lenet_eval: out_parts too small");
   dev(images, "images"); dev(labels, "labels"); dev(order, "order"); dev(out_parts, "out_parts");
-  TORCH_CHECK(order.numel() >= n && out_parts.numel() >= 2 * std::min<int64_t>(n, 256));
+  if (n > 0) {  // (grid 0: the plan's own)
+    const csed::LenetPlan plan =
+        csed::lenet_plan((int)n, 0, lcode(mfma_dtype), (int)kernel, false, false, false, false, false);
+    TORCH_CHECK(!plan.error, "lenet_eval: ", plan.error);
+    TORCH_CHECK(out_parts.numel() >= 2 * plan.grid, "lenet_eval: out_parts too small");
+  }
+  TORCH_CHECK(order.numel() >= n, "lenet_eval: order shorter than n");
   if (logp_out.has_value()) TORCH_CHECK(logp_out->numel() >= n * 10 && logp_out->scalar_type() == at::kFloat);
   const c10::DeviceGuard gd(images.device());
   CHECK_HIP(csed::launch_lenet_eval(images.data_ptr<uint8_t>(), labels.data_ptr<int64_t>(), order.data_ptr<int64_t>(),
@@ -1029,6 +1036,14 @@ TORCH_LIBRARY(csed, m) {
       .def("set_update", &LenetStepper::set_update)
       .def("run", &LenetStepper::run);
   m.def("lenet_layout() -> int[]", &lenet_layout);
+  m.def("lenet_plan(int B, int grid, int mfma_dtype, int kernel, bool staged, bool stage_next, bool cursor, bool train) "
+        "-> (int[], str)", &lenet_plan);
+  m.def("lenet_geometry(int B, int mfma_dtype, int grid, bool allow_split) -> int[]", &lenet_geometry);
+  m.def("lenet_tile_grid(int B) -> int", [](int64_t B) { return (int64_t)csed::lenet_tile_grid((int)B); });
+  m.def("conv2d_wgrad_workspace(int N, int IC, int KH, int KW, int OC) -> int",
+        [](int64_t N, int64_t IC, int64_t KH, int64_t KW, int64_t OC) {
+          return csed::conv2d_wgrad_workspace((int)N, (int)IC, (int)KH, (int)KW, (int)OC);
+        });
   m.def("conv_wgrad_prefetch(int depth=0) -> int", [](int64_t d) { return (int64_t)csed::conv_wgrad_prefetch((int)d); });
   m.def("preload_kernels(int device, int mask=127) -> float", &preload_kernels);
   m.def("lenet_zero_(Tensor(a!) t) -> ()", &lenet_zero_);

@@ -1415,7 +1415,6 @@ __device__ __forceinline__ void add4(float4& a, const float4& b) {
 // kernel's 1024 rows took a dozen dependent rounds, ~20 us at every epoch start of a large-batch
 // run); every thread issues all of its loads before its first store.
 // ---------------------------------------------------------------------------
-constexpr int STAGE_MAXB = 1024;  // staging rows (the tile kernel: 256 workgroups x 4 samples)
 constexpr int STAGE_ROWS = 16;    // rows per block
 constexpr int IMG_U4 = 784 / 16;  // 49 16-byte chunks per image
 
@@ -2400,31 +2399,20 @@ int64_t lenet_wimg_elems() { return I_END; }
 int64_t lenet_param_count() { return NP; }
 int64_t lenet_conv_param_count() { return CNP_PAD; }
 int64_t lenet_vec_len() { return VEC; }
-
-// the sample-tile kernel (lenet_tile.hip) for this launch?  kernel: 0 auto, 1 no, 2 yes
-// (a staged batch: the tile kernel's staging holds the first tile of every workgroup, rows
-// grid * lenet_tile_samples(); the per-sample kernel's one row per workgroup with grid == B or
-// split_k * B -- the kernel choice decides which, see csrc/bindings.cpp train_args)
-static bool use_tile(int kernel, int B, int mfma_dtype) {
-  if (mfma_dtype == kF32 || kernel == 1) return false;
-  return kernel == 2 || B >= kLenetTileMinB;
-}
+int64_t lenet_fc_part_elems() { return FC_PART_FLOATS + FC_TILES; }
 
 hipError_t launch_lenet_train(const LenetTrainArgs& a, hipStream_t s) {
-  if (a.mfma_dtype == kF32) return launch_lenet_train_f32(a, 0, nullptr, true, s);  // lenet_fused_f32.hip
-  if (use_tile(a.kernel, a.B, a.mfma_dtype)) return launch_lenet_tile(a, 0, nullptr, true, s);
-  // split step: a staged batch with SPLIT_K workgroups (parts) per sample, one staging row each
-  const bool split = a.xstage && a.lstage && a.grid == SPLIT_K * a.B && a.grid <= 256;
-  if (a.B <= 0 || a.grid <= 0 || (a.grid > a.B && !split)) return hipErrorInvalidValue;
-  // a staged batch has one sample per workgroup (the STAGED instantiation relies on it)
-  if (a.xstage && ((a.grid != a.B && !split) || !a.lstage)) return hipErrorInvalidValue;
+  const LenetPlan p = lenet_plan(a, true);
+  if (p.error) return hipErrorInvalidValue;
+  if (p.kernel == kLenetFp32) return launch_lenet_train_f32(a, p, 0, nullptr, true, s);  // lenet_fused_f32.hip
+  if (p.kernel == kLenetTile) return launch_lenet_tile(a, p, 0, nullptr, true, s);
   const size_t lds = (size_t)(S_TOTAL - S_X);  // dynamic activations; weights are static LDS
   CSED_DISPATCH_MFMA(a.mfma_dtype, {
-    if (split) {
+    if (p.variant == kLenetSplit) {  // SPLIT_K workgroups (parts) per sample, one staging row each
       CSED_ALLOW_LDS(lds, lenet_train_kernel<scalar_t, true, true, SPLIT_K>);
       hipLaunchKernelGGL((lenet_train_kernel<scalar_t, true, true, SPLIT_K>), dim3(a.grid), dim3(NT), lds, s,
                          a, 0, (float*)nullptr);
-    } else if (a.xstage) {
+    } else if (p.variant == kLenetStaged) {  // one sample per workgroup (the STAGED instantiation relies on it)
       CSED_ALLOW_LDS(lds, lenet_train_kernel<scalar_t, true, true>);
       hipLaunchKernelGGL((lenet_train_kernel<scalar_t, true, true>), dim3(a.grid), dim3(NT), lds, s, a, 0,
                          (float*)nullptr);
@@ -2537,12 +2525,9 @@ hipError_t launch_lenet_update(const LenetUpdateArgs& a, float* loss_parts, int 
 int64_t lenet_exch_words() { return EXCH_WORDS; }
 
 
-int lenet_stage_max_batch() { return STAGE_MAXB; }
-int lenet_split_k() { return SPLIT_K; }
-
 hipError_t launch_lenet_stage(const LenetStageArgs& a, const int64_t* cursor, hipStream_t s) {
   // rows: the staging rows (row r = sample r % B of the step); any batch size
-  if (a.B <= 0 || a.rows <= 0 || a.rows > STAGE_MAXB || !a.xstage || !a.lstage) return hipErrorInvalidValue;
+  if (a.B <= 0 || a.rows <= 0 || a.rows > kLenetStageMaxB || !a.xstage || !a.lstage) return hipErrorInvalidValue;
   hipLaunchKernelGGL(lenet_stage_kernel, dim3(cdiv(a.rows, STAGE_ROWS)), dim3(512), 0, s, a, cursor);
   return hipGetLastError();
 }
@@ -2568,12 +2553,12 @@ hipError_t launch_lenet_eval(const uint8_t* images, const int64_t* labels, const
   a.images = images; a.labels = labels; a.perm = order; a.cursor = nullptr; a.perm_len = n;
   a.B = (int)n; a.wimg = wimg; a.params = params; a.slab = nullptr; a.loss_acc = out;
   a.grad_scale = 0.f; a.mean = mean; a.std_ = std_; a.drop_p = 0.f; a.seed = 0; a.rng_offset = nullptr;
-  a.grid = (int)std::min<int64_t>(n, 256); a.mfma_dtype = mfma_dtype;
-  if (mfma_dtype == kF32) return launch_lenet_train_f32(a, logp_out ? 1 : 0, logp_out, false, s);
-  if (use_tile(kernel, a.B, mfma_dtype)) {
-    a.grid = lenet_tile_grid(a.B);  // == min(n, 256) for every n the auto mode sends here
-    return launch_lenet_tile(a, logp_out ? 1 : 0, logp_out, false, s);
-  }
+  a.mfma_dtype = mfma_dtype; a.kernel = kernel;
+  const LenetPlan p = lenet_plan(a, false);  // (grid 0: the plan's own)
+  if (p.error) return hipErrorInvalidValue;
+  a.grid = p.grid;
+  if (p.kernel == kLenetFp32) return launch_lenet_train_f32(a, p, logp_out ? 1 : 0, logp_out, false, s);
+  if (p.kernel == kLenetTile) return launch_lenet_tile(a, p, logp_out ? 1 : 0, logp_out, false, s);
   const size_t lds = (size_t)(S_TOTAL - S_X);
   CSED_DISPATCH_MFMA(mfma_dtype, {
     CSED_ALLOW_LDS(lds, lenet_train_kernel<scalar_t, false, false>);

@@ -845,14 +845,11 @@ __global__ void __launch_bounds__(NT, 1) lenet_train_f32_kernel(LenetTrainArgs a
 
 }  // namespace lenet32
 
-hipError_t launch_lenet_train_f32(const LenetTrainArgs& a, int write_logp, float* logp_out, bool train,
-                                  hipStream_t s) {
+hipError_t launch_lenet_train_f32(const LenetTrainArgs& a, const LenetPlan& p, int write_logp, float* logp_out,
+                                  bool train, hipStream_t s) {
   using namespace lenet32;
-  // split step: a staged batch with SPLIT_K workgroups (parts) per sample, one staging row each
-  const bool split = train && a.xstage && a.lstage && a.grid == SPLIT_K * a.B && a.grid <= 256;
-  if (a.B <= 0 || a.grid <= 0 || a.grid > 256 || (a.xstage && !split) || (!split && a.grid > a.B))
-    return hipErrorInvalidValue;
-  if (split) {
+  if (p.error || p.kernel != kLenetFp32) return hipErrorInvalidValue;
+  if (p.variant == kLenetSplit) {  // a staged batch with SPLIT_K workgroups (parts) per sample, one staging row each
     CSED_ALLOW_LDS(LDS_BYTES, lenet_train_f32_kernel<true, SPLIT_K>);
     hipLaunchKernelGGL((lenet_train_f32_kernel<true, SPLIT_K>), dim3(a.grid), dim3(NT), LDS_BYTES, s, a, 0,
                        (float*)nullptr);

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernels/lenet_plan.h"  // SPLIT_K
+
 namespace csed {
 namespace lenet {
 
@@ -62,9 +64,6 @@ constexpr int V_P2 = 0, V_DZ1 = 320, V_H = 384, V_DLOG = 448, VEC = 464;
 //    50..63, dlogits rows 10..15) stay zero; samples past B are stale and masked by the reader.
 __host__ __device__ constexpr int64_t vec16_index(int f, int b) { return ((int64_t)(b >> 2) * VEC + f) * 4 + (b & 3); }
 __host__ __device__ constexpr int64_t vec16_bytes(int B) { return (int64_t)((B + 63) & ~63) * VEC * 2; }
-
-// Split step: workgroups per sample (the backward conv stages are divided among them)
-constexpr int SPLIT_K = 4;
 
 }  // namespace lenet
 }  // namespace csed

@@ -50,7 +50,7 @@ namespace csed {
 namespace lenet_tile {
 
 using namespace csed::lenet;
-constexpr int TS = 4;               // samples per tile
+constexpr int TS = kLenetTileSamples;  // samples per tile
 constexpr int NT = 1024, NW = 16;   // 16 waves, 4 per SIMD
 constexpr int X_LD = 804;           // u16 per sample image (784 + pad; pitches: see XCP)
 // The normalised images are kept twice, the second copy shifted left by one pixel (X_1[i] =
@@ -861,17 +861,12 @@ __global__ void __launch_bounds__(NT, 1) lenet_tile_kernel(LenetTrainArgs a, int
 
 }  // namespace lenet_tile
 
-int lenet_tile_samples() { return lenet_tile::TS; }
-int lenet_tile_min_batch() { return kLenetTileMinB; }
-int lenet_tile_grid(int B) { return std::min(256, (B + lenet_tile::TS - 1) / lenet_tile::TS); }
-
-hipError_t launch_lenet_tile(const LenetTrainArgs& a, int write_logp, float* logp_out, bool train, hipStream_t s) {
+hipError_t launch_lenet_tile(const LenetTrainArgs& a, const LenetPlan& p, int write_logp, float* logp_out, bool train,
+                             hipStream_t s) {
   using namespace lenet_tile;
-  if (a.B <= 0 || a.grid != lenet_tile_grid(a.B) || a.mfma_dtype == kF32 || (a.xstage && !a.lstage) ||
-      (a.stage_next && (!a.xstage || !a.cursor)))
-    return hipErrorInvalidValue;
+  if (p.error || p.kernel != kLenetTile) return hipErrorInvalidValue;
   const size_t lds = (size_t)D_TOTAL;
-  const bool one = a.B <= TS * a.grid;
+  const bool one = p.one_tile;
 #define CSED_TILE_LAUNCH(TR, ONE, WL, LP)                                                           \
   do {                                                                                               \
     CSED_ALLOW_LDS(lds, lenet_tile_kernel<scalar_t, TR, ONE>);                                    \

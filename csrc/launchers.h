@@ -9,11 +9,9 @@
 #include <stdint.h>
 
 #include "comm/ipc_allreduce.h"
+#include "kernels/lenet_plan.h"  // the dtype codes; which kernel / grid / staging a fused LeNet launch gets
 
 namespace csed {
-
-// dtype codes shared with Python (see ops/_dtypes.py)
-enum : int { kF32 = 0, kBF16 = 1, kF16 = 2, kU8 = 3 };
 
 // ---------------------------------------------------------------- data ----
 // out[b, :] = (src[idx[b], :] / 255 - mean) / std, converted to out_dtype.
@@ -226,39 +224,42 @@ struct LenetTrainArgs {
   int mfma_dtype;
   uint64_t* dbg;             // optional [grid, 16] stage stamps (diagnostics)
   uint64_t* dbg_entry;       // optional [grid, 16]: each wave's s_memtime at kernel entry (split step)
-  uint8_t* xstage;           // optional staged batch [B, 784] (grid == B): sample b = workgroup b
-  int64_t* lstage;           // its labels [B]
+  uint8_t* xstage;           // optional staged batch [rows, 784], rows = the launch's LenetPlan::stage_rows
+                             // (row r = sample r % B: grid == B or, split step, SPLIT_K * B; the tile kernel: row
+                             // g * tile_samples + s = sample s of workgroup g's first tile)
+  int64_t* lstage;           // its labels [rows]
   int stage_next;            // with xstage: also stage step cursor+1 (perm / cursor are read for it)
   int kernel;                // 0 auto, 1 per-sample lenet_train, 2 sample-tile kernel (lenet_tile.hip)
 };
-// mfma_dtype == kF32 selects the exact-fp32 kernel (lenet_fused_f32.hip: no weight images,
-// no batch staging, v_mfma_f32_16x16x4_f32).
+// The plan of a launch with these arguments (kernels/lenet_plan.h).
+inline LenetPlan lenet_plan(const LenetTrainArgs& a, bool train) {
+  return lenet_plan(a.B, a.grid, a.mfma_dtype, a.kernel, a.xstage != nullptr, a.lstage != nullptr, a.stage_next != 0,
+                    a.cursor != nullptr, train);
+}
+// Runs the kernel lenet_plan picks (hipErrorInvalidValue where the plan has an error): the per-sample
+// lenet_train, the sample-tile kernel (lenet_tile.hip: tiles of kLenetTileSamples samples, grid
+// lenet_tile_grid(B), same outputs) or, mfma_dtype == kF32, the exact-fp32 kernel (lenet_fused_f32.hip:
+// no weight images, v_mfma_f32_16x16x4_f32; it stages its batch only in the split step).
 hipError_t launch_lenet_train(const LenetTrainArgs& a, hipStream_t s);
-// Sample-tile training / evaluation kernel for large batches (lenet_tile.hip): tiles of
-// lenet_tile_samples() samples, grid lenet_tile_grid(B); same outputs as lenet_train.  The auto
-// mode picks it for 16-bit, unstaged batches of at least kLenetTileMinB samples.
-constexpr int kLenetTileMinB = 1024;
-int lenet_tile_samples();
-int lenet_tile_min_batch();
-int lenet_tile_grid(int B);
-hipError_t launch_lenet_tile(const LenetTrainArgs& a, int write_logp, float* logp_out, bool train, hipStream_t s);
-hipError_t launch_lenet_train_f32(const LenetTrainArgs& a, int write_logp, float* logp_out, bool train,
-                                  hipStream_t s);
+// The other two kernels' launches of an already resolved, valid plan p of (a, train).
+hipError_t launch_lenet_tile(const LenetTrainArgs& a, const LenetPlan& p, int write_logp, float* logp_out, bool train,
+                             hipStream_t s);
+hipError_t launch_lenet_train_f32(const LenetTrainArgs& a, const LenetPlan& p, int write_logp, float* logp_out,
+                                  bool train, hipStream_t s);
 // Batch staging: pixels + labels of one step, gathered through the epoch permutation.
 struct LenetStageArgs {
   const uint8_t* images; const int64_t* labels; const int64_t* perm; int64_t perm_len;
-  int B;                     // <= lenet_stage_max_batch()
+  int B;
   uint8_t* xstage; int64_t* lstage;
-  int rows;                  // staging rows (0 = B); row r holds sample r % B (split step: SPLIT_K * B)
+  int rows;                  // staging rows (<= kLenetStageMaxB); row r holds sample r % B (split step: SPLIT_K * B)
 };
-int lenet_split_k();         // workgroups per sample of the split step (grid = split_k * B)
-int lenet_stage_max_batch();
 // Gather the batch of step cursor[0] (no counter change).
 hipError_t launch_lenet_stage(const LenetStageArgs& a, const int64_t* cursor, hipStream_t s);
 int64_t lenet_wimg_elems();
 int64_t lenet_param_count();
 int64_t lenet_conv_param_count();  // 5280: conv1.w, conv1.b, conv2.w, conv2.b
 int64_t lenet_vec_len();           // 464 floats of per-sample fc vectors
+int64_t lenet_fc_part_elems();     // floats of lenet_update's split-K fc scratch (LenetUpdateArgs::fc_part)
 // Fused slab reduce + SGD + weight-image refresh + counter bump.
 // apply_sgd = 0: write the reduced gradient to grad_out (DDP: all-reduce next).
 // apply_sgd = 1: grad = grad_in if given (after the all-reduce) else the slab sum.

@@ -26,6 +26,37 @@ def test_layout_names_every_value(schemas):
     assert tuple(fused.lenet_layout()) == tuple(int(v) for v in torch.ops.csed.lenet_layout())
 
 
+def test_plan_and_geometry_name_every_value(schemas):
+    """LenetPlan / LenetGeometry: one field per value of csed::lenet_plan (its integers, then the message) and
+    csed::lenet_geometry, and the wrappers return exactly those values.  No GPU: integer arguments only."""
+    ops = torch.ops.csed
+    values, error = ops.lenet_plan(1024, 256, 1, 0, True, True, True, True)
+    assert len(fused.LenetPlan._fields) == len(values) + 1
+    assert tuple(fused.lenet_plan(1024, 256, 1, 0, True, True, True, True)) == (*(int(v) for v in values), error) \
+        == (fused.TILE, fused.STRIDED, 256, 1, 1024, "")
+    assert "256 workgroups" in fused.lenet_plan(65, 260, 1, 0, True).error
+    geo = ops.lenet_geometry(8, 1, 0, True)
+    assert len(fused.LenetGeometry._fields) == len(geo)
+    assert tuple(fused.lenet_geometry(8, 1)) == tuple(int(v) for v in geo) == (32, 1, 1, 0, 32)
+    lay = fused.lenet_layout()
+    assert lay.vec_len == 464 and lay.fc_part_elems == 8 * 88 * 256 + 88
+    assert [fused.tile_grid(B) for B in (1, 4, 5, 1023, 1024, 8192)] == [1, 1, 2, 256, 256, 256]
+
+
+@pytest.mark.parametrize("shape", [(1, 5, 5, 10), (10, 5, 5, 20)])
+def test_wgrad_workspace_is_the_extensions(schemas, shape):
+    """ops/functional.py wgrad_workspace_elems is csed::conv2d_wgrad_workspace, for the two LeNet convs
+    (IC, KH, KW, OC): one [OC, IC * KH * KW + 1] slab per block, never more than 256 blocks."""
+    from csed_514_project_distributed_training_using_pytorch_amd.ops.functional import wgrad_workspace_elems
+
+    IC, KH, KW, OC = shape
+    slab = OC * (IC * KH * KW + 1)
+    for N in (1, 255, 256, 257, 2047, 2048, 5000):
+        n = wgrad_workspace_elems(N, IC, KH, KW, OC)
+        assert n == torch.ops.csed.conv2d_wgrad_workspace(N, IC, KH, KW, OC)
+        assert n % slab == 0 and 1 <= n // slab <= min(N, 256)
+
+
 @pytest.mark.parametrize("method,op", [("set_train", "train"), ("set_update", "update")])
 def test_stepper_takes_the_op_argument_lists(schemas, method, op):
     """LenetStepper.set_train / set_update: the ops' argument types, in order (after the object itself)."""

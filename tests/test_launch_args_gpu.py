@@ -1,6 +1,7 @@
-"""FusedLeNetTrainer.train_args / update_args on a real engine: global batch 8 on 64 synthetic images,
-the smallest staged split-step shape (4 workgroups per sample), where the staging and grid derivation
-of the builders can go wrong."""
+"""FusedLeNetTrainer.train_args / update_args on real engines: global batch 8 on 64 synthetic images, the
+smallest staged split-step shape (4 workgroups per sample), where the staging and grid derivation of the
+builders can go wrong; the engine's geometry on either side of every threshold of the launch plan
+(csrc/kernels/lenet_plan.h); and the launches the plan rejects."""
 import pytest
 import torch
 
@@ -9,6 +10,24 @@ from csed_514_project_distributed_training_using_pytorch_amd.engine.fused import
 from csed_514_project_distributed_training_using_pytorch_amd.models import Net
 
 pytestmark = pytest.mark.gpu
+
+STATE = ("params", "momentum", "wimg", "step", "cursor", "rng", "loss", "xstage", "lstage")
+
+
+def _eager_and_stepper_agree(eng, n):
+    """One eager step and one native-executor step from the same state: bitwise the same state after."""
+    eng.set_epoch_order(torch.arange(n))
+    state = eng._state()
+    start = [t.clone() for t in state]
+    eng.step()
+    eager = [t.clone() for t in state]
+    for t, v in zip(state, start):
+        t.copy_(v)
+    eng.stepper().run(1)
+    torch.cuda.synchronize()
+    assert eng.cursor.item() == 1 and not torch.equal(eng.flat.data, start[0])
+    for name, a, b in zip(STATE, eager, state):
+        assert torch.equal(a, b), name
 
 
 def test_builder_modes_and_stepper_matches_eager_step():
@@ -29,18 +48,70 @@ def test_builder_modes_and_stepper_matches_eager_step():
     assert apply.grad_in is g and apply.grad_out is None and apply.apply_sgd is True
     assert apply.loss_parts is None and apply.loss_acc is None and apply.nparts == 0
 
-    # one eager step and one native-executor step from the same state: bitwise the same state after
-    eng.set_epoch_order(torch.arange(64))
-    state = eng._state()
-    start = [t.clone() for t in state]
-    eng.step()
-    eager = [t.clone() for t in state]
-    for t, v in zip(state, start):
-        t.copy_(v)
-    eng.stepper().run(1)
-    torch.cuda.synchronize()
-    assert eng.cursor.item() == 1 and not torch.equal(eng.flat.data, start[0])
-    for name, a, b in zip(("params", "momentum", "wimg", "step", "cursor", "rng", "loss", "xstage", "lstage"),
-                          eager, state):
-        assert torch.equal(a, b), name
+    _eager_and_stepper_agree(eng, 64)
     eng.close()
+
+
+# (dtype, per-rank batch) -> grid, split, staged, tile_staged, staging rows, tile kernel, training kernel: the
+# engine's defaults on either side of each threshold (split step up to 64, staging up to 256, tile kernel from 1024;
+# fp32 stages only in the split step)
+BOUNDARIES = {
+    (torch.bfloat16, 8): (32, True, True, False, 32, False, "lenet_train"),
+    (torch.bfloat16, 64): (256, True, True, False, 256, False, "lenet_train"),
+    (torch.bfloat16, 65): (65, False, True, False, 65, False, "lenet_train"),
+    (torch.bfloat16, 256): (256, False, True, False, 256, False, "lenet_train"),
+    (torch.bfloat16, 257): (256, False, False, False, 0, False, "lenet_train"),
+    (torch.bfloat16, 1023): (256, False, False, False, 0, False, "lenet_train"),
+    (torch.bfloat16, 1024): (256, False, False, True, 1024, True, "lenet_tile"),
+    (torch.float32, 64): (256, True, True, False, 256, False, "lenet_train_f32"),
+    (torch.float32, 65): (65, False, False, False, 0, False, "lenet_train_f32"),
+}
+
+
+@pytest.mark.parametrize("dtype,B", list(BOUNDARIES), ids=lambda v: str(v).replace("torch.", ""))
+def test_engine_geometry_at_the_plan_boundaries(dtype, B):
+    grid, split, staged, tile_staged, rows, tile, kernel = BOUNDARIES[dtype, B]
+    torch.manual_seed(1)
+    eng = FusedLeNetTrainer(Net().to("cuda:0"), synthetic_mnist(2 * B, seed=3), global_batch=B, compute_dtype=dtype)
+    assert (eng.grid, eng.split, eng.staged, eng.tile_staged) == (grid, split, staged, tile_staged)
+    assert (0 if eng.xstage is None else eng.xstage.shape[0]) == rows
+    assert (0 if eng.lstage is None else eng.lstage.shape[0]) == rows
+    assert eng.uses_tile_kernel() is tile and eng.kernel_names == kernel + " + lenet_update"
+    assert (eng.train_args().xstage is not None) == (rows > 0)
+    _eager_and_stepper_agree(eng, 2 * B)
+    eng.close()
+
+
+def test_rejected_launches_raise_before_anything_is_enqueued():
+    """Launches the plan calls invalid raise from the op's argument checks, each naming the rule; nothing
+    reaches the device, so the engine trains on afterwards."""
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(1)
+    data = synthetic_mnist(64, seed=3)
+    eng = FusedLeNetTrainer(Net().to(dev), data, global_batch=8)  # staged split step: B 8, grid 32
+    f32 = FusedLeNetTrainer(Net().to(dev), data, global_batch=8, compute_dtype=torch.float32, split=False)
+    assert not f32.staged and f32.grid == 8
+    eng.set_epoch_order(torch.arange(64))
+    staged, unstaged = eng.train_args(stage_next=True), dict(xstage=None, lstage=None, stage_next=False)
+    xs, ls = torch.zeros(8, 784, dtype=torch.uint8, device=dev), torch.zeros(8, dtype=torch.long, device=dev)
+    cases = [
+        (staged._replace(kernel=2), "sample-tile kernel runs grid"),  # kernel 2 off the tile grid
+        (staged._replace(B=1024, grid=200, kernel=0, **unstaged), "sample-tile kernel runs grid"),  # auto, B 1024
+        (f32.train_args()._replace(xstage=xs, lstage=ls), "fp32 stages its batch only in the split step"),
+        (staged._replace(B=65, grid=260), "at most 256 workgroups"),
+        (staged._replace(lstage=None), "xstage and lstage go together"),
+        (staged._replace(**unstaged), "grid <= B"),
+        (staged._replace(cursor=None), "stage_next needs"),
+    ]
+    before = eng.flat.data.clone()
+    for args, message in cases:
+        with pytest.raises(RuntimeError, match=message):
+            torch.ops.csed.lenet_train(*args)
+    torch.cuda.synchronize()
+    assert torch.equal(eng.flat.data, before) and eng.cursor.item() == 0
+    eng.step()
+    torch.cuda.synchronize()
+    assert eng.cursor.item() == 1 and not torch.equal(eng.flat.data, before)
+    assert torch.isfinite(eng.flat.data).all()
+    eng.close()
+    f32.close()

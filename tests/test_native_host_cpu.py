@@ -28,6 +28,22 @@ def test_slab_layout_under_host_sanitizers(tmp_path):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+def test_launch_plan_under_host_sanitizers(tmp_path):
+    """csrc/kernels/lenet_plan.h under ASan + UBSan: every plan it calls valid keeps the kernels' invariants, and
+    the engine's default geometry at each threshold is the hand-written table (tests/native/plan_check.cpp)."""
+    exe = tmp_path / "plan_check"
+    cmd = [HIPCC, "-O1", "-g", "-std=c++17", "-fno-gpu-sanitize", "-fsanitize=address,undefined",
+           "-fno-sanitize-recover=all", f"-I{os.path.join(ROOT, 'csrc')}",
+           os.path.join(ROOT, "tests", "native", "plan_check.cpp"), "-o", str(exe)]
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "plan check ok" in r.stdout
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 def test_synth_generator_under_host_sanitizers(tmp_path):
     """csrc/data/synth_mnist.cpp under ASan + UBSan: the bilinear resampler's taps stay inside the
     bordered source image for every sample, and the sanitized build produces exactly

@@ -23,8 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from csed_514_project_distributed_training_using_pytorch_amd.data import synthetic_mnist  # noqa: E402
-from csed_514_project_distributed_training_using_pytorch_amd.engine.fused import (  # noqa: E402
-    FusedLeNetTrainer, lenet_layout, tile_grid)
+from csed_514_project_distributed_training_using_pytorch_amd.engine.fused import FusedLeNetTrainer  # noqa: E402
 from csed_514_project_distributed_training_using_pytorch_amd.models import Net  # noqa: E402
 
 
@@ -85,8 +84,7 @@ def main():
             n = args.steps
             dt = torch.zeros(n, eng.grid * 32, dtype=torch.long, device=dev)
             du = torch.zeros(n, 8 * 1024, dtype=torch.long, device=dev)
-            kern = eng.kernel_for(B, eng.grid)
-            tile = B >= lenet_layout().tile_min_batch and kern != 1 and eng.grid == tile_grid(B)
+            tile = eng.uses_tile_kernel()
             i_in, i_out = (12, 13) if tile else (22, 23)
             # fc_blocks(B) (lenet_fused.hip): 88 FC tiles, 8 / waves-per-tile of them per block
             wpt = 1 if B <= 128 else 2 if B <= 256 else 4 if B <= 512 else 8

@@ -46,4 +46,4 @@ for B in (64, 1024, 8192):
             n = p.numel()
             out.append(f"{name} {rel(g[off:off + n].view_as(p), p.grad):.2e} (1/B in-kernel {rel(g_pre[off:off + n].view_as(p), p.grad):.2e})")
             off += n
-        print(f"B={B} {str(dt)[6:]:9s} kernel={'tile' if eng.kernel_for(B, eng.grid) == 0 and B >= 1024 else 'per-sample'}: " + ", ".join(out), flush=True)
+        print(f"B={B} {str(dt)[6:]:9s} kernel={'tile' if eng.uses_tile_kernel() else 'per-sample'}: " + ", ".join(out), flush=True)
