@@ -351,16 +351,15 @@ bool linear_lsm_nll_ok(const Tensor& x, const Tensor& w) {
 // nn.Linear's backward (y = act(x W^T + b), dy [M, O], x [M, I], w [O, I]): dx = gate(dy) W and
 // dw = gate(dy)^T x with db as the ones column, gate(dy) = dy * (y > 0) * gate_scale when the
 // forward had an activation.  One launch when both GEMMs fit the small-GEMM path.
-void linear_bwd(const Tensor& dy, const Tensor& x, const Tensor& w, const optional<Tensor>& gate, double gate_scale,
-                const optional<Tensor>& dx, const optional<Tensor>& dw, const optional<Tensor>& db,
-                int64_t mfma_dtype, const optional<Tensor>& lsm_target, const optional<Tensor>& lsm_gout,
-                double lsm_div) {
+std::vector<csed::GemmArgs> linear_bwd_gemms(const Tensor& dy, const Tensor& x, const Tensor& w,
+                                             const optional<Tensor>& gate, double gate_scale,
+                                             const optional<Tensor>& dx, const optional<Tensor>& dw,
+                                             const optional<Tensor>& db, int64_t mfma_dtype) {
   dev(dy, "dy"); dev(x, "x"); dev(w, "w");
   TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && w.dim() == 2 && dy.size(0) == x.size(0) && w.size(0) == dy.size(1) &&
               w.size(1) == x.size(1), "linear_bwd: shape mismatch");
   if (gate.has_value()) dev(*gate, "gate");
   TORCH_CHECK(!db.has_value() || dw.has_value(), "linear_bwd: db rides on the dw GEMM");
-  const c10::DeviceGuard gd(dy.device());
   const optional<Tensor> none;
   std::vector<csed::GemmArgs> todo;
   if (dx.has_value()) {
@@ -372,6 +371,39 @@ void linear_bwd(const Tensor& dy, const Tensor& x, const Tensor& w, const option
     const optional<Tensor> gt = gate.has_value() ? optional<Tensor>(gate->t()) : none;
     todo.push_back(make_gemm(dy.t(), x, *dw, none, 1.0, 0.0, 0, 0.0, 0, 0, none, gt, gate_scale, mfma_dtype, db));
   }
+  return todo;
+}
+
+std::vector<int64_t> plan_ints(const csed::GemmPlan& p) {
+  return {p.small, p.splits, p.tiles, p.grid_x, p.grid_y, p.a_mode, p.b_mode};
+}
+
+// csed::GemmPlan of the launch gemm makes for these tensors (ops/plans.py GemmPlan)
+std::vector<int64_t> gemm_plan(const Tensor& A, const Tensor& B, const Tensor& C, const optional<Tensor>& gate,
+                               int64_t mfma_dtype, const optional<Tensor>& rowsum) {
+  const optional<Tensor> none;
+  return plan_ints(csed::gemm_plan(make_gemm(A, B, C, none, 1.0, 0.0, 0, 0.0, 0, 0, none, gate, 1.0, mfma_dtype, rowsum)));
+}
+
+// [one launch for both GEMMs (the pair kernel), then each GEMM's plan] of linear_bwd on these tensors
+std::vector<int64_t> linear_bwd_plan(const Tensor& dy, const Tensor& x, const Tensor& w, const optional<Tensor>& gate,
+                                     const optional<Tensor>& dx, const optional<Tensor>& dw, const optional<Tensor>& db,
+                                     int64_t mfma_dtype) {
+  const std::vector<csed::GemmArgs> todo = linear_bwd_gemms(dy, x, w, gate, 1.0, dx, dw, db, mfma_dtype);
+  std::vector<int64_t> v = {todo.size() == 2 && csed::gemm_pairable(todo[0], todo[1])};
+  for (const auto& a : todo)
+    for (int64_t i : plan_ints(csed::gemm_plan(a))) v.push_back(i);
+  return v;
+}
+
+void linear_bwd(const Tensor& dy, const Tensor& x, const Tensor& w, const optional<Tensor>& gate, double gate_scale,
+                const optional<Tensor>& dx, const optional<Tensor>& dw, const optional<Tensor>& db,
+                int64_t mfma_dtype, const optional<Tensor>& lsm_target, const optional<Tensor>& lsm_gout,
+                double lsm_div) {
+  // (the GEMMs: dx = gate(dy) W, then dw = gate(dy)^T x with db as the ones column)
+  std::vector<csed::GemmArgs> todo = linear_bwd_gemms(dy, x, w, gate, gate_scale, dx, dw, db, mfma_dtype);
+  const c10::DeviceGuard gd(dy.device());
+  const optional<Tensor> none;
   if (lsm_target.has_value()) {  // dy holds the head's log-probs: the GEMMs read d nll(log_softmax) / dz
     TORCH_CHECK(lsm_gout.has_value() && lsm_gout->numel() == 1 && lsm_gout->scalar_type() == at::kFloat &&
                     dy.scalar_type() == at::kFloat && !gate.has_value() && lsm_target->scalar_type() == at::kLong &&
@@ -1084,6 +1116,9 @@ TORCH_LIBRARY(csed, m) {
   m.def("gemm(Tensor A, Tensor B, Tensor(a!) C, Tensor? bias, float alpha, float beta, int act, float drop_p, "
         "int seed, int offset, Tensor? offset_dev, Tensor? gate, float gate_scale, int mfma_dtype, "
         "Tensor(b!)? rowsum=None) -> ()");
+  m.def("gemm_plan(Tensor A, Tensor B, Tensor C, Tensor? gate, int mfma_dtype, Tensor? rowsum=None) -> int[]", &gemm_plan);
+  m.def("linear_bwd_plan(Tensor dy, Tensor x, Tensor w, Tensor? gate, Tensor? dx, Tensor? dw, Tensor? db, "
+        "int mfma_dtype) -> int[]", &linear_bwd_plan);
   m.def("colsum(Tensor x, Tensor? gate, float gate_scale, Tensor(a!) out, float beta) -> ()");
   m.def("conv2d_fwd(Tensor x, Tensor w, Tensor? bias, Tensor(a!) y, int pad, Tensor(b!)? idx, Tensor? chscale, "
         "int pool_k, int mfma_dtype, float drop2d_p=0.0, int seed=0, int offset=0, Tensor? offset_dev=None, "

@@ -967,21 +967,37 @@ int gemm_splits(const GemmArgs& a) {
   return std::max(1, std::min(s, 64));
 }
 
-static GemmArgs with_modes(const GemmArgs& in) {
-  GemmArgs a = in;
-  a.a_mode = pick_mode(a.A, a.a_dtype, a.sam, a.sak, a.mfma_dtype);
-  a.b_mode = pick_mode(a.B, a.b_dtype, a.sbn, a.sbk, a.mfma_dtype);
+// What a launch of these arguments runs (launchers.h GemmPlan): the launchers below dispatch on it
+GemmPlan gemm_plan(const GemmArgs& a) {
+  GemmPlan p{};
+  const int Np = a.N + (a.rowsum ? 1 : 0);
+  p.small = gemm_small(a);
+  p.splits = gemm_splits(a);
+  p.grid_x = p.small ? cdiv(Np, 16) : cdiv(Np, BN);
+  p.grid_y = p.small ? cdiv(a.M, 16) : cdiv(a.M, BM);
+  p.tiles = p.grid_x * p.grid_y;
+  p.a_mode = pick_mode(a.A, a.a_dtype, a.sam, a.sak, a.mfma_dtype);
+  p.b_mode = pick_mode(a.B, a.b_dtype, a.sbn, a.sbk, a.mfma_dtype);
   // the gate is loaded with A's mode: it must allow the same vector access
-  if (a.G && pick_mode(a.G, a.g_dtype, a.sam, a.sak, a.mfma_dtype) != a.a_mode) a.a_mode = kScalar;
-  if (gemm_small(a)) {
+  if (a.G && pick_mode(a.G, a.g_dtype, a.sam, a.sak, a.mfma_dtype) != p.a_mode) p.a_mode = kScalar;
+  if (p.small) {
     // (vector fragment loads where the operand is K-contiguous, aligned, in the compute dtype or fp32)
-    if (a.a_mode != kKContig) a.a_mode = kScalar;
-    if (a.b_mode != kKContig) a.b_mode = kScalar;
+    if (p.a_mode != kKContig) p.a_mode = kScalar;
+    if (p.b_mode != kKContig) p.b_mode = kScalar;
   }
-  return a;
+  return p;
 }
 
-static int small_tiles(const GemmArgs& a) { return cdiv(a.M, 16) * cdiv(a.N + (a.rowsum ? 1 : 0), 16); }
+static GemmArgs with_modes(const GemmArgs& in, const GemmPlan& p) {
+  GemmArgs a = in;
+  a.a_mode = p.a_mode;
+  a.b_mode = p.b_mode;
+  return a;
+}
+static GemmArgs with_modes(const GemmArgs& in) { return with_modes(in, gemm_plan(in)); }
+
+// a small GEMM's workgroups inside the pair / MLP-head launches: the plan's tile count, from the one place
+static int small_tiles(const GemmArgs& a) { return gemm_plan(a).tiles; }
 
 bool gemm_pairable(const GemmArgs& a, const GemmArgs& b) {
   return a.M > 0 && a.N > 0 && b.M > 0 && b.N > 0 && gemm_small(a) && gemm_small(b) &&
@@ -1065,16 +1081,17 @@ hipError_t launch_gemm(const GemmArgs& in, hipStream_t s) {
   if (in.M <= 0 || in.N <= 0) return hipSuccess;
   if (in.head_part && !gemm_head_ok(in)) return hipErrorInvalidValue;
   if (in.lsm_target && (!gemm_small(in) || in.a_dtype != kF32 || in.G)) return hipErrorInvalidValue;
-  const GemmArgs a = with_modes(in);
+  const GemmPlan p = gemm_plan(in);
+  const GemmArgs a = with_modes(in, p);
   const int Np = a.N + (a.rowsum ? 1 : 0);
-  if (gemm_small(a)) {
+  if (p.small) {
     CSED_DISPATCH_COMPUTE(a.mfma_dtype, {
-      hipLaunchKernelGGL(gemm_small_kernel<scalar_t>, dim3(cdiv(a.M, 16) * cdiv(Np, 16)), dim3(256), 0, s, a);
+      hipLaunchKernelGGL(gemm_small_kernel<scalar_t>, dim3(p.tiles), dim3(256), 0, s, a);
     });
     return hipGetLastError();
   }
-  const int splits = a.ws ? gemm_splits(a) : 1;
-  dim3 grid(cdiv(Np, BN), cdiv(a.M, BM), splits);
+  const int splits = a.ws ? p.splits : 1;  // (split-K needs the caller's workspace)
+  dim3 grid(p.grid_x, p.grid_y, splits);
   CSED_DISPATCH_COMPUTE(a.mfma_dtype, {
     hipLaunchKernelGGL(gemm_kernel<scalar_t>, grid, dim3(256), 0, s, a);
     if (splits > 1)

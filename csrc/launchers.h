@@ -113,6 +113,18 @@ bool gemm_head_ok(const GemmArgs& a);
 // Number of K splits launch_gemm will use for these shapes (1 = no workspace needed).
 int gemm_splits(const GemmArgs& a);
 bool gemm_is_small(const GemmArgs& a);  // the small-GEMM path (few 16 x 16 tiles, K <= 1024)
+// What launch_gemm runs for these arguments; the launcher dispatches on it and Python asks through
+// csed::gemm_plan (ops/plans.py GemmPlan).  Host logic only: pointers are looked at (alignment), not read.
+struct GemmPlan {
+  int small;           // gemm_small_kernel (one workgroup per 16 x 16 tile), else gemm_kernel (64 x 64 tiles)
+  int splits;          // K splits of gemm_kernel (1: none, no reduce launch) = gemm_splits(a), whether or not
+                       // a.ws is set: launch_gemm without a workspace runs 1 split whatever this says
+                       // (the gemm op always allocates one when this is > 1)
+  int tiles;           // output tiles = grid_x * grid_y, the rowsum column included
+  int grid_x, grid_y;  // tiles along N / M
+  int a_mode, b_mode;  // operand staging: 0 scalar, 1 vectors along K, 2 vectors along the rows
+};
+GemmPlan gemm_plan(const GemmArgs& a);
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s);
 // Two independent GEMMs of the small-GEMM path in one launch (nn.Linear's backward); pairable ==
 // both fit that path (few 16 x 16 tiles, K <= 1024) with the same compute dtype.

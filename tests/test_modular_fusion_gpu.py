@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from csed_514_project_distributed_training_using_pytorch_amd import ops
-from csed_514_project_distributed_training_using_pytorch_amd.ops import _native
+from csed_514_project_distributed_training_using_pytorch_amd.ops import _native, plans
 from csed_514_project_distributed_training_using_pytorch_amd.ops.functional import wgrad_workspace_elems
 
 pytestmark = pytest.mark.gpu
@@ -123,6 +123,7 @@ def test_linear_bwd_pair_matches_two_gemms(dt, act, mio):
     gs = 2.0 if act == 2 else 1.0
     o = _native.ops()
     dx1, dw1, db1 = torch.empty_like(x), torch.empty_like(w), torch.empty(O, device=DEV)
+    assert plans.linear_bwd_plan(dy, x, w, dt, gate, dx1, dw1, db1).pairable == 1  # (the pair kernel's launch)
     o.linear_bwd(dy, x, w, gate, gs, dx1, dw1, db1, MF[dt])
     dx2, dw2, db2 = torch.empty_like(x), torch.empty_like(w), torch.empty(O, device=DEV)
     o.gemm(dy, w, dx2, None, 1.0, 0.0, 0, 0.0, 0, 0, None, gate, gs, MF[dt])
