@@ -11,22 +11,16 @@ see csrc/kernels/lenet_fused.hip) at any world size:
 The data-parallel gradient all-reduce (ref src/train_dist.py:83, DDP's one
 87,360-byte bucket) is fused into lenet_update: each update lane pushes its
 rank-local gradient value straight into every peer's IPC-mapped receive buffer
-and sums what the peers pushed (csrc/comm buffers, LL-tagged words).  It is
-enabled after a collective bring-up and an exact self-test; if either fails, or
-``CSED_ALLREDUCE=rccl`` asks for it, the step runs as the fallback
-
-    lenet_update (reduce only) -> RCCL all-reduce -> SGD kernel
-
-In ``auto`` mode with one rank per GPU (a real node, pushes over xGMI) both
-steps are then timed at bring-up -- one 16-step graph each -- and the faster is
-kept, so a fused exchange slower than RCCL is never locked in (SURVEY §7.3 step
-6).  ``CSED_TIME_PATHS``: ``auto`` (default: time exactly then), ``1`` (always
-time, also on ranks sharing a GPU, and also time an exchange-free step), ``0``
-(never: a passing self-test keeps the fused path).
+and sums what the peers pushed (csrc/comm buffers, LL-tagged words).  Its
+bring-up and path timing are in engine/exchange_bringup.py; where it is off the
+step runs as lenet_update (reduce only) -> RCCL all-reduce -> SGD kernel.
 
 All per-step state (batch cursor into this rank's epoch permutation, Philox
 offset, optimizer step) lives on the device, so a sequence of steps is
-captured once into a HIP graph and replayed with no host work per step.
+captured once into a HIP graph and replayed with no host work per step
+(engine/replay.py).  A step is described once, as the list of its launches
+(``_step_launches``): that list is what runs, and its ``launch_key`` is what the
+cached graphs and the native executor are looked up by.
 
 The model's parameters are re-homed into the engine's flat fp32 buffer, so the
 ``Net`` module always sees the current weights (checkpointing, evaluation
@@ -50,69 +44,11 @@ from ..ops import _native
 from ..parallel import comm as _comm
 from ..parallel.comm import DistContext
 from ..parallel import ipc as _ipc
-from ..parallel.ipc import allreduce_mode, open_exchange, open_loopback_exchange, wait_timeout_s
+from ..parallel.ipc import allreduce_mode, open_loopback_exchange, wait_timeout_s
 from ..utils.flat import FlatParams
-
-_HIP_LIBS: list | None = None
-
-
-def _hip_libs() -> list:
-    """ctypes handles of the HIP runtime this process already loaded (via torch), never a second
-    copy."""
-    global _HIP_LIBS
-    if _HIP_LIBS is None:
-        import ctypes
-
-        try:
-            with open("/proc/self/maps") as f:
-                paths = {ln.split()[-1] for ln in f if "libamdhip64.so" in ln}
-            _HIP_LIBS = [ctypes.CDLL(p) for p in sorted(paths)]
-        except OSError:
-            _HIP_LIBS = []
-    return _HIP_LIBS
-
-
-def _clear_hip_error() -> None:
-    """Reset this thread's sticky HIP error after a failed stream capture.  Our ops report
-    ``hipGetLastError()`` after each launch, so an invalidated capture would otherwise
-    surface as a failure of the next (eager) launch."""
-    for lib in _hip_libs():
-        lib.hipGetLastError()
-
-
-class NativeGraph:
-    """A step graph captured with ``torch.classes.csed.HipGraph`` (csrc/bindings.cpp), replayed by
-    one ctypes ``hipGraphLaunch`` on the current stream (the ScriptObject keeps the graph alive)."""
-
-    _launch = None
-
-    def __init__(self, obj, device: torch.device):
-        import ctypes
-
-        self.obj = obj
-        self.device_index = device.index
-        self.exec = ctypes.c_void_p(obj.exec_handle())
-        if NativeGraph._launch is None:
-            fn = _hip_libs()[0].hipGraphLaunch
-            fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
-            NativeGraph._launch = fn
-
-    def replay(self) -> None:
-        e = NativeGraph._launch(self.exec, torch._C._cuda_getCurrentRawStream(self.device_index))
-        if e != 0:
-            raise RuntimeError(f"hipGraphLaunch failed ({e})")
-
-    def num_nodes(self) -> int:
-        return int(self.obj.num_nodes())
-
-
-def _hip_graph_upload(exec_handle: int, stream: int) -> bool:
-    """hipGraphUpload of an instantiated graph on a stream (CSED_GRAPH_UPLOAD=1)."""
-    import ctypes
-
-    fn = _hip_libs()[0].hipGraphUpload
-    fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
-    return fn(ctypes.c_void_p(exec_handle), ctypes.c_void_p(stream)) == 0
+from . import exchange_bringup as _bringup
+from . import replay as _replay
+from .replay import launch_key
 
 
 class LenetLayout(NamedTuple):
@@ -290,7 +226,8 @@ class FusedLeNetTrainer:
         t_mark = time.perf_counter()
         self.repack()  # (the extension's first kernel launch: its code object loads here)
         self.bringup_s["first_kernel"] = time.perf_counter() - t_mark
-        self._graphs: dict[tuple, object] = {}  # torch.cuda.CUDAGraph (or NativeGraph)
+        # both caches are keyed on launch_key of the launches they replay; invalidate() empties them
+        self._graphs: dict[tuple, object] = {}  # torch.cuda.CUDAGraph (or replay.NativeGraph), see graph()
         self._warmed: set[str] = set()  # step kinds whose capture warm-up has run (see _capture)
         self._cap_stream: torch.cuda.Stream | None = None
         self._stepper: tuple | None = None  # (key, csed.LenetStepper), see stepper()
@@ -327,7 +264,7 @@ class FusedLeNetTrainer:
         elif multi:
             self._xdiag["ranks_per_gpu"] = _ipc.ranks_per_gpu(self.ctx)  # (collective: every rank)
             if mode in ("auto", "fused"):
-                self._enable_exchange(required=(mode == "fused"))
+                _bringup.enable_exchange(self, required=(mode == "fused"))
             else:
                 self._xdiag["ipc_open"] = f"not tried (CSED_ALLREDUCE={mode})"
         # Loopback exchange (one GPU, no process group): lenet_update runs its full push + poll
@@ -387,203 +324,34 @@ class FusedLeNetTrainer:
         return "rccl"
 
     # ------------------------------------------------- fused gradient exchange
-    def _enable_exchange(self, required: bool) -> None:
-        """Bring up lenet_update's in-kernel exchange (collective on every rank): open the IPC
-        buffers and self-test them with the update kernel itself.  Then (auto mode, RCCL, see
-        the module docstring for ``CSED_TIME_PATHS``) the fused and fallback steps are timed
-        and the faster is kept."""
-        import time
-
-        t0 = time.perf_counter()
-        xd = self._xdiag
-        xd["peer_access"] = _ipc.peer_access(self.device)
-        ex, why = open_exchange(self.ctx, lenet_layout().exch_words, shared=self._xdiag.get("ranks_per_gpu"))
-        hook = _ipc.test_reject_hook()
-        last = self.ctx.rank == self.ctx.world_size - 1
-        if hook == "open":  # (test hook: the last rank's mapping "fails"; every rank votes)
-            ok_local = not last
-            if not self._vote(ok_local) and ex is not None:
-                ex.close()
-                ex, why = None, "open: test hook CSED_TEST_EXCH_REJECT=open on the last rank"
-        xd["ipc_open"] = "ok" if ex is not None else (why or "failed")
-        t1 = time.perf_counter()
-        self.bringup_s["ipc_open"] = t1 - t0
-        ok = ex is not None
-        if ok:
-            self.exch = ex
-            local_ok = self._exchange_self_test()
-            if hook == "selftest" and last:
-                local_ok = False
-            xd["self_test"] = bool(local_ok)
-            ok = self._vote(local_ok)
-            if not ok:
-                why = "self-test mismatch or timeout on some rank"
-                xd["self_test_all_ranks"] = False
-        self.bringup_s["self_test"] = time.perf_counter() - t1
-        if not ok:
-            if ex is not None:
-                try:
-                    ex.close()  # collective: every rank opened it (a failed rank's buffer too)
-                except Exception:
-                    pass
-            self.exch = None
-            self.exchange_note = f"fused exchange off: {why}; fallback {self.allreduce_kind}"
-            if required:
-                raise RuntimeError(f"CSED_ALLREDUCE=fused but the fused exchange is unusable ({why})")
-            return
-        self.exchange_note = "fused exchange on (self-test passed)"
-        tp = os.environ.get("CSED_TIME_PATHS", "auto").strip().lower()
-        if not required and tp != "0":
-            # (every rank takes the same branch: ranks_per_gpu is the group's value).  On gloo
-            # (ranks sharing a GPU, a rehearsal) only CSED_TIME_PATHS=1 times: the fallback step's
-            # host all-reduce cannot be captured, so it times as inf and the fused path is kept --
-            # what the rehearsal measures is the selection's own bring-up cost
-            do_time = tp == "1" or (self.ctx.backend == "nccl" and self._xdiag.get("ranks_per_gpu") == 1)
-        else:
-            do_time = False
-        if do_time and self.ctx.control is not None:
-            # lazy RCCL (bench.py at N > 1): the fallback step's all-reduce would create the RCCL
-            # communicator (1-3.6 s) in the middle of the bring-up -- the selection is deferred to
-            # select_path(), which the bench runs after epoch 0 (outside the reference span)
-            self._path_pending = tp
-            self.exchange_note = "fused exchange on (self-test passed; path timing deferred)"
-        elif do_time:
-            self._select_path_now(tp)
-
     def select_path(self) -> bool:
         """Run the fused-vs-RCCL step timing deferred by a lazy-RCCL bring-up (collective; a no-op
         otherwise).  True if the step path changed (the cached graphs are dropped then)."""
         tp, self._path_pending = self._path_pending, None
         if tp is None or self.exch is None:
             return False
-        self._select_path_now(tp)
+        _bringup.select_path_now(self, tp)
         if self.exch is None:
-            self._graphs.clear()
-            self._stepper = None
+            self.invalidate()
             return True
         return False
 
-    def _select_path_now(self, tp: str) -> None:
-        import time
-
-        t2 = time.perf_counter()
-        t_fused = self._time_steps()
-        saved, self.exch = self.exch, None
-        # (gloo: the host all-reduce is not capturable -- not timed, the fused path is kept)
-        t_fallback = self._time_steps() if self.ctx.backend == "nccl" else float("inf")
-        t_local = float("inf")
-        if tp == "1":
-            # the same step with no exchange at all (each rank updates on its own gradient;
-            # the state is restored): fused - local = what the exchange costs per step
-            self.comm = False
-            t_local = self._time_steps()
-            self.comm = True
-        # a path whose graph could not be captured times as inf; ties keep the fused path
-        self.exch = saved if t_fused <= t_fallback else None
-        if self.exch is None:
-            self.exchange_note = "fused exchange off: slower than the fallback step"
-            # every rank finished the timing above (device synchronize before the timing
-            # all-reduce), so no peer still pushes into these buffers: the close is safe
-            saved.close()
-        else:
-            self.exchange_note = "fused exchange on (self-test passed, timed faster than the fallback)"
-        fin = lambda t: round(t, 2) if t != float("inf") else None  # noqa: E731
-        self.path_timing_us = {"fused_step_us": fin(t_fused), "fallback_step_us": fin(t_fallback),
-                               "local_step_us": fin(t_local),
-                               "exchange_us": fin(t_fused - t_local) if max(t_fused, t_local) != float("inf")
-                               else None,
-                               "fallback": "rccl", "kept": "fused" if self.exch is not None else "rccl"}
-        self.bringup_s["path_timing"] = time.perf_counter() - t2
-
     def exchange_diag(self) -> dict:
-        """This rank's data-parallel diagnostics (``parallel/ipc.py`` DIAG_KEYS): the bring-up's
-        stage results plus the exchange's current error word and first recorded mismatch."""
-        d = _ipc.empty_diag(self.ctx)
-        d.update(self._xdiag)
-        d["device_count"] = torch.cuda.device_count()
-        d["path_timing_us"] = self.path_timing_us
-        d["allreduce"] = self.allreduce_kind
-        d["note"] = self.exchange_note
-        if self.exch is not None:
-            d["error_word"] = self.comm_errors()
-            d["first_mismatch"] = self.comm_diag()
-        return d
+        """This rank's data-parallel diagnostics (``parallel/ipc.py`` DIAG_KEYS)."""
+        return _bringup.exchange_diag(self)
 
-    def _vote(self, ok: bool) -> bool:
-        t = torch.tensor([1 if ok else 0], dtype=torch.int32, device=_comm.ctl_device(self.ctx))
-        _comm.ctl_all_reduce(self.ctx, t, dist.ReduceOp.MIN)
-        return bool(t.item())
-
-    def _exchange_self_test(self, rounds: int = 2) -> bool:
-        """Integer-valued slabs through lenet_update with and without the exchange: the
-        exchanged gradient must equal the process group's sum of the local ones exactly
-        (both slot parities, every rank).  Runs the same collectives on every rank.  The operands
-        come from the extension's own fill kernel (csed::lenet_selftest_fill: small integers, a
-        hash of the element index, the round and the rank) and the results are compared on the
-        host, so the bring-up launches no torch kernel (each is a code object loaded at its first
-        launch, ms apiece -- the round-5 self-test drew its values with torch.randint)."""
-        import numpy as np
-
-        ops = torch.ops.csed
-        pg_dev = _comm.ctl_device(self.ctx)
-        raw = dict(with_loss=False, grad_scale=1.0)  # (plain slab sums; the local one without the split-K scratch)
-        ok = True
-        # every round's local and exchanged gradients first, then ONE process-group all-reduce of
-        # all the local ones (a collective round trip per round was most of the self-test's time)
-        local = torch.empty(rounds, N_PARAMS, dtype=torch.float32, device=self.device)
-        fused = torch.empty_like(local)
-        for r in range(rounds):
-            ops.lenet_selftest_fill(self.slab, self.vslab, self.B, self.mfma, 977 + 31 * self.ctx.rank + 7919 * r)
-            ops.lenet_update(*self.update_args("reduce", grad=local[r], exchange=False, fc_split=False, **raw))
-            try:
-                ops.lenet_update(*self.update_args("reduce", grad=fused[r], exchange=True, **raw))
-            except Exception:
-                ok = False
-        ref = local.to(pg_dev, copy=True)
-        _comm.ctl_all_reduce(self.ctx, ref)
-        ok &= bool(np.array_equal(fused.cpu().numpy(), ref.cpu().numpy()))
-        torch.cuda.synchronize(self.device)
-        try:
-            ok &= self.exch.error(reset=True) == 0
-        except Exception:
-            ok = False
-        _native.zero_(self.vslab)
-        return ok
-
-    def _time_steps(self, nsteps: int = 16, reps: int = 3) -> float:
-        """us per training step of a captured graph (max over ranks); engine state is restored."""
-        state = self._state()
-        saved = [t.clone() for t in state]
-        try:
-            g = self._capture(nsteps)
-        except Exception as e:  # same code on every rank: every rank lands here
-            print(f"[csed] step-graph capture failed while timing ({e!r})", file=sys.stderr)
-            _clear_hip_error()
-            g = None
-        us = float("inf")
-        if g is not None:
-            g.replay()
-            torch.cuda.synchronize(self.device)
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(reps):
-                g.replay()
-            b.record()
-            b.synchronize()
-            us = a.elapsed_time(b) * 1e3 / (reps * nsteps)
-            del g
-        for t, v in zip(state, saved):
-            t.copy_(v)
-        torch.cuda.synchronize(self.device)
-        t = torch.tensor([us], dtype=torch.float64, device=_comm.ctl_device(self.ctx))
-        _comm.ctl_all_reduce(self.ctx, t, dist.ReduceOp.MAX)
-        return float(t.item())
+    def invalidate(self) -> None:
+        """Drop (and free) the captured graphs and the native executor.  Their keys follow every change
+        the step's arguments show; this is for the ones they cannot show -- an exchange remapped behind
+        the same id, an epoch order of another length taking ``perm``'s place -- and for letting go of
+        what will not be replayed again."""
+        self._graphs.clear()
+        self._stepper = None
 
     def close(self) -> None:
         """Release the graphs and the IPC buffers (collective on every rank: a barrier runs
         first so that no peer is still pushing into this rank's buffers)."""
-        self._graphs.clear()
-        self._stepper = None
+        self.invalidate()
         if self.loopback_world and self.exch is not None:  # local buffer, no peers
             torch.cuda.synchronize(self.device)
             self.exch.close()
@@ -614,8 +382,7 @@ class FusedLeNetTrainer:
         if self.exch is None:
             raise RuntimeError("no IPC exchange to inject a fault into")
         self.exch.mute(on)
-        self._graphs.clear()
-        self._stepper = None
+        self.invalidate()
 
     # ----------------------------------------------------------------- state
     def repack(self) -> None:
@@ -642,11 +409,10 @@ class FusedLeNetTrainer:
             order.copy_(host, non_blocking=True)
         else:
             order = order.to(self.device, torch.long).contiguous()
-        if self._graphs and order.numel() != self.perm.numel():
-            self._graphs.clear()  # captured pointers refer to the old buffer
         if order.numel() == self.perm.numel():
             self.perm.copy_(order)
         else:
+            self.invalidate()  # captured pointers refer to the old buffer
             self.perm = order
         _native.zero_(self.cursor)
         self._stage_current()
@@ -742,17 +508,34 @@ class FusedLeNetTrainer:
             grad_post=grad_scale if reduces and not in_kernel else 1.0, fc_part=self.fc_part if fc_split else None,
             lr_table=None if sch is None else sch.table, lr_pos=None if sch is None else sch.pos)
 
-    def _launch_step(self, perm: torch.Tensor, **kw) -> None:
-        """A step's launches on ``perm``; ``kw``: B, grid, cursor, grad_scale where not the full step's."""
-        ops = torch.ops.csed
+    def _step_launches(self, perm: torch.Tensor | None = None, **kw) -> list[tuple]:
+        """A step's launches on ``perm`` (default: the epoch order), in order, as (name, arguments): ops of
+        the extension, and "all_reduce" on the flat gradient.  ``kw``: B, grid, cursor, grad_scale where not
+        the full step's.  What _launch_step runs and what graph() keys on (replay.launch_key)."""
         # full steps read the staged batch and stage the next one; the epoch's short tail uses perm
-        ops.lenet_train(*self.train_args(perm=perm, stage_next=True, **kw))
+        train = ("lenet_train", self.train_args(perm=perm, stage_next=True, **kw))
         if self.exch is not None or not self.comm:  # one kernel: the fused exchange, or no exchange at all
-            ops.lenet_update(*self.update_args("step", **kw))
-        else:
-            ops.lenet_update(*self.update_args("reduce", grad=self.flat.grad, **kw))
-            dist.all_reduce(self.flat.grad, op=dist.ReduceOp.SUM)
-            ops.lenet_update(*self.update_args("apply", grad=self.flat.grad, **kw))
+            return [train, ("lenet_update", self.update_args("step", **kw))]
+        g = self.flat.grad
+        return [train, ("lenet_update", self.update_args("reduce", grad=g, **kw)), ("all_reduce", (g,)),
+                ("lenet_update", self.update_args("apply", grad=g, **kw))]
+
+    def _tail_launches(self) -> list[tuple]:
+        """The launches of the epoch's short last batch."""
+        rem = self.tail_size()
+        tail = self.perm[self.full_steps() * self.B:]  # a view: stable pointer for graph replay
+        gb = rem * self.world * max(1, self.loopback_world)  # (the sampler pads to a multiple: same on every rank)
+        # the tail step does not use the cursor; keep it consistent for the next epoch
+        return (self._step_launches(tail, B=rem, grid=min(rem, self.grid), cursor=None, grad_scale=1.0 / gb)
+                + [("lenet_add_", (self.cursor, 1))])
+
+    @staticmethod
+    def _launch_step(launches: list[tuple]) -> None:
+        for name, args in launches:
+            if name == "all_reduce":
+                dist.all_reduce(*args, op=dist.ReduceOp.SUM)
+            else:
+                getattr(torch.ops.csed, name)(*args)
 
     def _stages(self, kernel: int) -> bool:
         """Whether a full step launched with ``kernel`` (kernel_for) reads / writes the staging
@@ -784,19 +567,14 @@ class FusedLeNetTrainer:
 
     def step(self) -> None:
         """One full-batch training step at the device cursor (eager launches)."""
-        self._launch_step(self.perm)
+        self._launch_step(self._step_launches())
 
     def tail_size(self) -> int:
         """Per-rank samples of the epoch's short last batch (0 if the epoch divides evenly)."""
         return self.perm.numel() - self.full_steps() * self.B
 
     def _tail_step(self) -> None:
-        rem = self.tail_size()
-        tail = self.perm[self.full_steps() * self.B:]  # a view: stable pointer for graph replay
-        gb = rem * self.world * max(1, self.loopback_world)  # (the sampler pads to a multiple: same on every rank)
-        self._launch_step(tail, B=rem, grid=min(rem, self.grid), cursor=None, grad_scale=1.0 / gb)
-        # the tail step does not use the cursor; keep it consistent for the next epoch
-        torch.ops.csed.lenet_add_(self.cursor, 1)
+        self._launch_step(self._tail_launches())
 
     def last_partial_step(self, use_graph: bool = True) -> None:
         """The epoch's final short batch (ref DataLoader drop_last=False semantics); replayed
@@ -820,104 +598,25 @@ class FusedLeNetTrainer:
         self.bringup_s[key] = self.bringup_s.get(key, 0.0) + dt
 
     def _capture(self, nsteps: int, tail: bool = False):
-        """Capture ``nsteps`` full steps (or the epoch's tail step) into a HIP graph.
-
-        The first capture of each step kind (full / tail x all-reduce path x kernel) runs one eager warm-up step on the
-        capture stream first (lazy RCCL communicator set-up, each kernel's first-launch symbol
-        lookup -- neither may happen inside a capture), the engine state snapshotted before and
-        restored after it; later captures of the same kind skip it.  The capture calls
-        capture_begin / capture_end directly: ``torch.cuda.graph``'s device synchronize and
-        ``empty_cache`` are not needed (the steps allocate nothing).
-
-        ``CSED_NATIVE_GRAPH=1`` captures a native HIP graph instead (``torch.classes.csed.HipGraph``,
-        replayed by a ctypes hipGraphLaunch): it skips torch's capture_begin generator set-up (a
-        torch fill kernel, ~5 ms of first-launch code-object load in the reference span), but
-        measured on one box its replays start later -- 14.9-15.7 vs 14.1-14.5 us per step in the
-        driver's 20-step window, 13.34 vs 13.26 us at 3000 steps (profiles/r6/graph_ab.log) -- so
-        torch's graphs stay the default.  ``CSED_GRAPH_UPLOAD=1`` uploads each graph after its
-        instantiation (no measured effect on the first replay).  Host seconds accumulate in
-        ``bringup_s``: capture.stream / .warmup(.snapshot/.step/.sync/.restore) / .record /
-        .instantiate / .upload."""
+        """Capture ``nsteps`` full steps (or the epoch's tail step) into a HIP graph (replay.capture) on
+        the engine's capture stream.  The first capture of each step kind (full / tail x all-reduce path x
+        kernel) warms the step up there."""
         import time
 
-        step = self._tail_step if tail else self.step
-        cur = torch.cuda.current_stream(self.device)
         t0 = time.perf_counter()
         if self._cap_stream is None:  # (one capture stream per engine: creating a stream costs ms)
             self._cap_stream = torch.cuda.Stream(self.device)
-        s = self._cap_stream
         kind = f"{'tail' if tail else 'full'}/{self.allreduce_kind}/{self.train_kernel}"
         self._stamp("capture.stream", time.perf_counter() - t0)
-        if kind not in self._warmed:
-            # snapshot the state the capture warm-up will advance; the side stream must
-            # wait for the snapshot copies too (they are enqueued on the current stream)
-            ta = time.perf_counter()
-            state = self._state()
-            saved = [t.clone() for t in state]
-            s.wait_stream(cur)
-            tb = time.perf_counter()
-            with torch.cuda.stream(s):
-                step()
-            cur.wait_stream(s)
-            tc = time.perf_counter()
-            torch.cuda.synchronize(self.device)
-            td = time.perf_counter()
-            for t, v in zip(state, saved):
-                t.copy_(v)
-            torch.cuda.synchronize(self.device)
-            te = time.perf_counter()
-            self._warmed.add(kind)
-            for k, dt in (("snapshot", tb - ta), ("step", tc - tb), ("sync", td - tc), ("restore", te - td)):
-                self._stamp(f"capture.warmup.{k}", dt)
-        t1 = time.perf_counter()
-        _comm.quiesce()  # (no pending collective for the watchdog to query during the capture)
-        # thread_local: only this thread's unsafe calls invalidate the capture.  The process
-        # group's watchdog thread keeps querying the events of earlier collectives while a step
-        # that contains an RCCL all-reduce is captured; in the default (global) mode that query
-        # invalidates the capture and the watchdog then aborts the process (seen on the GPU box,
-        # profiles/round5.md)
-        if os.environ.get("CSED_NATIVE_GRAPH") == "1":
-            ng = torch.classes.csed.HipGraph()  # (csrc/bindings.cpp)
-            with torch.cuda.stream(s):
-                ng.begin(self.device.index)
-                try:
-                    for _ in range(nsteps):
-                        step()
-                finally:
-                    ng.end()  # (ends the capture even after a failed step; raises if it was invalidated)
-            t2 = t3 = time.perf_counter()  # (end() instantiated it)
-            if os.environ.get("CSED_GRAPH_UPLOAD", "0") == "1":
-                with torch.cuda.stream(cur):
-                    ng.upload()
-            g = NativeGraph(ng, self.device)
-        else:
-            g = torch.cuda.CUDAGraph(keep_graph=True)
-            with torch.cuda.stream(s):
-                g.capture_begin(capture_error_mode="thread_local")
-                try:
-                    for _ in range(nsteps):
-                        step()
-                finally:
-                    g.capture_end()
-            t2 = time.perf_counter()
-            g.instantiate()
-            t3 = time.perf_counter()
-            if os.environ.get("CSED_GRAPH_UPLOAD", "0") == "1":
-                _hip_graph_upload(g.raw_cuda_graph_exec(), cur.cuda_stream)
-        t4 = time.perf_counter()
-        for k, dt in (("warmup", t1 - t0), ("record", t2 - t1), ("instantiate", t3 - t2), ("upload", t4 - t3)):
-            self._stamp(f"capture.{k}", dt)
+        g = _replay.capture(self._tail_step if tail else self.step, nsteps, self._cap_stream,
+                            None if kind in self._warmed else self._state(), self._stamp)
+        self._warmed.add(kind)
         return g
 
-    def _schedule_key(self) -> tuple:
-        """The schedule buffers a captured launch points at (a schedule whose state was reloaded with
-        a table of another length has new ones)."""
-        sch = self.lr_schedule
-        return () if sch is None else (sch.table.data_ptr(), sch.table.numel(), sch.pos.data_ptr())
-
     def graph(self, nsteps: int, tail: bool = False):
-        """The captured graph of ``nsteps`` full steps (or of the epoch's tail step), cached."""
-        key = (nsteps, self.perm.data_ptr(), self.perm.numel(), self.B, tail, self._schedule_key())
+        """The captured graph of ``nsteps`` full steps (or of the epoch's tail step), cached under what its
+        launches point at and hold."""
+        key = (nsteps, tail, launch_key(self._tail_launches() if tail else self._step_launches()))
         if key in self._graphs:
             return self._graphs[key]
         if self.allreduce_kind == "rccl" and dist.is_initialized() and dist.get_backend() == "gloo":
@@ -930,21 +629,13 @@ class FusedLeNetTrainer:
         except Exception as e:  # RCCL capture unsupported -> eager fallback
             print(f"[csed] HIP graph capture failed ({e!r}); running steps eagerly", file=sys.stderr)
             self.capture_comm_ok = False
-            _clear_hip_error()
+            _replay._clear_hip_error()
             torch.cuda.synchronize(self.device)
             return None
         self._graphs[key] = g
         return g
 
-    @staticmethod
-    def graph_plan(k: int, steps_per_graph: int) -> list[int]:
-        """Graph sizes that run k steps: whole graphs of min(spg, k) steps, then one graph for
-        the remainder (never a run of 1-step replays)."""
-        if k <= 0:
-            return []
-        spg = max(1, min(steps_per_graph, k))
-        full, rem = divmod(k, spg)
-        return [spg] * full + ([rem] if rem else [])
+    graph_plan = staticmethod(_replay.graph_plan)
 
     def prepare(self, steps_per_graph: int = 16, ks: tuple[int, ...] = (), tail: bool = True) -> None:
         """Capture up front (capture is never inside a timed region) every graph that
@@ -965,13 +656,13 @@ class FusedLeNetTrainer:
         C++.  None where a step is more than two launches (the all-reduce fallback)."""
         if self.comm and self.exch is None:
             return None
-        key = (self.perm.data_ptr(), -1 if self.exch is None else self.exch.id, self.staged, self.train_kernel,
-               self._schedule_key())
+        # (the split-K fc scratch also next to the exchange, where the launcher does not use it)
+        train, update = self.train_args(stage_next=True), self.update_args("step", fc_split=True)
+        key = launch_key((train, update))
         if self._stepper is None or self._stepper[0] != key:
             st = torch.classes.csed.LenetStepper()
-            st.set_train(*self.train_args(stage_next=True))
-            # (the split-K fc scratch also next to the exchange, where the launcher does not use it)
-            st.set_update(*self.update_args("step", fc_split=True))
+            st.set_train(*train)
+            st.set_update(*update)
             self._stepper = (key, st)
         return self._stepper[1]
 
@@ -1071,8 +762,7 @@ class FusedLeNetTrainer:
         self.step_count.fill_(1 if have else 0)
         g = sd["param_groups"][0]
         self.lr, self.momentum = float(g["lr"]), float(g["momentum"])
-        self._graphs.clear()
-        self._stepper = None  # the executor's argument blocks hold lr / momentum
+        self.invalidate()  # (what held the old lr / momentum is not replayed again)
 
     def set_lr_schedule(self, schedule) -> None:
         """Train at ``schedule``'s rates (optim.LRSchedule, moved to the engine's device) from its current
@@ -1081,8 +771,7 @@ class FusedLeNetTrainer:
         native-executor run, train at different rates.  Captured graphs and the executor's argument
         blocks hold the old rate or table: dropped, as in load_optimizer_state_dict."""
         self.lr_schedule = None if schedule is None else schedule.to(self.device)
-        self._graphs.clear()
-        self._stepper = None
+        self.invalidate()
 
     def params_changed(self) -> None:
         """Call after writing the model parameters from outside (e.g. a checkpoint load)."""

@@ -168,7 +168,7 @@ class ModularTrainer:
             comm.quiesce()  # (no pending collective for the watchdog to query during the capture)
             graph = torch.cuda.CUDAGraph()
             # thread_local: the process group's watchdog thread may query earlier collectives'
-            # events during the capture (see engine/fused.py _capture)
+            # events during the capture (see engine/replay.py capture)
             with torch.cuda.graph(graph, stream=s, capture_error_mode="thread_local"):
                 sloss = self._step(sx, st)
             torch.cuda.synchronize(dev)

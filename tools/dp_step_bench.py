@@ -5,7 +5,7 @@
 Paths: ``fused`` (exchange inside lenet_update: 2 kernels per step), ``ipc``
 (reduce-only update -> one-shot IPC all-reduce kernel -> SGD kernel) and, on an
 RCCL process group, ``rccl`` (same with RCCL's all-reduce).  Each is timed as
-graph-replayed steps (engine._time_steps, max over ranks).  With --gloo the
+graph-replayed steps (exchange_bringup.time_steps, max over ranks).  With --gloo the
 bootstrap group is gloo and the ranks may share one GPU (their kernels then
 compete for it, and the transport is local HBM, not xGMI).
 """
@@ -19,6 +19,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 from csed_514_project_distributed_training_using_pytorch_amd.data import synthetic_mnist  # noqa: E402
+from csed_514_project_distributed_training_using_pytorch_amd.engine.exchange_bringup import time_steps  # noqa: E402
 from csed_514_project_distributed_training_using_pytorch_amd.engine.fused import FusedLeNetTrainer  # noqa: E402
 from csed_514_project_distributed_training_using_pytorch_amd.models import Net  # noqa: E402
 from csed_514_project_distributed_training_using_pytorch_amd.parallel.comm import DistContext  # noqa: E402
@@ -30,7 +31,7 @@ def main():
     ap.add_argument("--gloo", action="store_true")
     ap.add_argument("--global-batch", type=int, default=64)
     ap.add_argument("--steps", type=int, default=32)
-    ap.add_argument("--no-time-steps", action="store_true", help="skip engine._time_steps (bench.py's order)")
+    ap.add_argument("--no-time-steps", action="store_true", help="skip time_steps (bench.py's order)")
     args = ap.parse_args()
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     local = int(os.environ.get("LOCAL_RANK", rank))
@@ -52,7 +53,7 @@ def main():
         smp = ShardSampler(len(data), world, rank, shuffle=True, seed=42)
         smp.set_epoch(0)
         eng.set_epoch_order(smp.indices())
-        us = float("nan") if args.no_time_steps else eng._time_steps(nsteps=args.steps, reps=10)
+        us = float("nan") if args.no_time_steps else time_steps(eng, nsteps=args.steps, reps=10)
         # the same steps the way bench.py runs them: cached graphs, wall clock
         eng.prepare(args.steps)
         eng.run_steps(4 * args.steps, args.steps)
