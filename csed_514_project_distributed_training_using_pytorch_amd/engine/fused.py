@@ -63,6 +63,10 @@ class LenetLayout(NamedTuple):
     tile_samples: int  # samples per tile of the sample-tile training kernel (csrc/kernels/lenet_tile.hip)
     tile_min_batch: int  # smallest per-rank batch the auto mode runs on the sample-tile kernel
     fc_part_elems: int  # floats of lenet_update's split-K fc scratch (partial sums, then the tiles' arrival counters)
+    fc_tiles: int  # lenet_update's FC tiles (one arrival counter each)
+    conv_blocks: int  # lenet_update's CONV blocks (they follow the launch's FC blocks)
+    fc_counters_off: int  # float offset of the fc_tiles int32 arrival counters inside the scratch
+    fc_part_min_batch: int  # per-rank batch from which the engine allocates the scratch
 
 
 @functools.lru_cache(maxsize=None)
@@ -89,6 +93,26 @@ class LenetPlan(NamedTuple):
     error: str  # "" for a valid launch, else the rule it breaks
 
 
+UPDATE_SGD, UPDATE_EXCHANGE, UPDATE_SPLIT_K, UPDATE_PLAIN = 0, 1, 2, 3  # LenetUpdatePlan.form
+
+
+class LenetUpdatePlan(NamedTuple):
+    """What one ``csed::lenet_update`` launch runs: ``csed::lenet_update_plan``'s values, in its order
+    (csrc/kernels/lenet_plan.h, the rule the launcher itself dispatches on)."""
+    form: int  # UPDATE_SGD (lenet_sgd_kernel on grad_in), else lenet_update_kernel: UPDATE_EXCHANGE / SPLIT_K / PLAIN
+    world_bound: int  # the exchange's world rounded up to 2 / 4 / 8 (0: no exchange)
+    loopback: int
+    sched: int  # the learning rate comes from the device-resident schedule
+    blocks: int  # the grid: fc_blocks FC blocks, then the layout's conv_blocks
+    fc_blocks: int
+    waves_per_tile: int  # waves that split one FC tile's K
+    tiles_per_block: int
+    slices: int  # split-K batch slices per FC tile (1: unsplit)
+    fc_tpb: int  # the kernel's trailing arguments: tiles per block fixed by the launcher (0: derived from B) ...
+    fc_sl: int  # ... and the slices
+    error: str  # "" for a valid launch, else the rule it breaks
+
+
 class LenetGeometry(NamedTuple):
     """The engine's default full step at a per-rank batch: ``csed::lenet_geometry``'s values, in its order."""
     grid: int
@@ -111,6 +135,23 @@ def lenet_geometry(B: int, mfma: int, grid: int = 0, allow_split: bool = True) -
     """The default geometry at per-rank batch B (``grid`` 0: min(B, 256)).  No GPU needed."""
     _native.require()
     return LenetGeometry(*(int(v) for v in torch.ops.csed.lenet_geometry(B, mfma, grid, allow_split)))
+
+
+def lenet_update_plan(B: int, *, apply_sgd: bool = True, grad_in: bool = False, vslab: bool = True, exch_world: int = 0,
+                      exch_loopback: bool = False, exch_cap: int | None = None, exch_timeout: bool = True,
+                      lr_table: bool = False, lr_pos: bool | None = None, ticket: bool = True, lr_len: int | None = None,
+                      fc_part_n: int = 0, forced_slices: int = -1) -> LenetUpdatePlan:
+    """The plan of a ``csed::lenet_update`` launch at per-rank batch B, from what the launcher looks at: which
+    optional arguments are set, the exchange's world (0: none), loopback flag and words per sender (default: the
+    layout's), the schedule's length, the floats of the split-K scratch (0: none) and the forced slice count
+    (default -1: this process's CSED_FC_SLICES, as the launcher reads it).  No GPU needed."""
+    _native.require()
+    values, error = torch.ops.csed.lenet_update_plan(
+        B, apply_sgd, grad_in, vslab, exch_world, exch_loopback,
+        lenet_layout().exch_words if exch_cap is None else exch_cap, exch_timeout, lr_table,
+        lr_table if lr_pos is None else lr_pos, ticket, int(lr_table) if lr_len is None else lr_len, fc_part_n,
+        forced_slices)
+    return LenetUpdatePlan(*(int(v) for v in values), error)
 
 
 @functools.lru_cache(maxsize=None)
@@ -212,12 +253,12 @@ class FusedLeNetTrainer:
         self.rng_offset = _native.zeros(1, torch.long, dev)
         self.eval_parts = _native.zeros(2 * 256, torch.float32, dev)
         self.perm = _native.arange(self.B, dev)
-        # split-K fc-gradient scratch (lenet_fused.hip fc_split_slices): per-rank batches > 1024
-        # without the fused exchange form the fc weight gradients as up to 8 batch slices per
-        # tile on all CUs, the tile's last slice finishing it (8 x 88 tiles x 256 partial sums,
-        # then 88 arrival counters that must start at zero)
-        self.fc_part = (_native.zeros((lay.fc_part_elems + 127) // 128 * 128, torch.float32, dev) if self.B > 1024
-                        else None)
+        # split-K fc-gradient scratch (lenet_plan.h lenet_update_plan): per-rank batches from
+        # fc_part_min_batch without the fused exchange form the fc weight gradients as up to 8 batch
+        # slices per tile on all CUs, the tile's last slice finishing it (8 x 88 tiles x 256 partial
+        # sums, then 88 arrival counters that must start at zero)
+        self.fc_part = (_native.zeros((lay.fc_part_elems + 127) // 128 * 128, torch.float32, dev)
+                        if self.B >= lay.fc_part_min_batch else None)
         # one staging row per workgroup (split step: row r holds sample r % B), or the tile kernel's
         # grid * tile_samples rows
         srows = geo.stage_rows
@@ -507,6 +548,22 @@ class FusedLeNetTrainer:
             exch_id=-1 if exch is None else exch.id, exch_timeout_s=2.0 if exch is None else self.exch_timeout_s,
             grad_post=grad_scale if reduces and not in_kernel else 1.0, fc_part=self.fc_part if fc_split else None,
             lr_table=None if sch is None else sch.table, lr_pos=None if sch is None else sch.pos)
+
+    def update_plan(self, args: UpdateArgs) -> LenetUpdatePlan:
+        """The plan of the ``csed::lenet_update`` launch that ``args`` (update_args) describes."""
+        exch = args.exch_id >= 0
+        return lenet_update_plan(
+            args.B, apply_sgd=args.apply_sgd, grad_in=args.grad_in is not None, vslab=args.vslab is not None,
+            exch_world=(self.loopback_world or self.world) if exch else 0,
+            exch_loopback=exch and bool(self.loopback_world), exch_timeout=args.exch_timeout_s > 0,
+            lr_table=args.lr_table is not None, lr_pos=args.lr_pos is not None, ticket=args.ticket is not None,
+            lr_len=0 if args.lr_table is None else args.lr_table.numel(),
+            fc_part_n=0 if args.fc_part is None else args.fc_part.numel())
+
+    def fc_counters(self) -> torch.Tensor:
+        """The split-K scratch's per-tile arrival counters (an int32 view of fc_part; zero between launches)."""
+        lay = lenet_layout()
+        return self.fc_part[lay.fc_counters_off:lay.fc_counters_off + lay.fc_tiles].view(torch.int32)
 
     def _step_launches(self, perm: torch.Tensor | None = None, **kw) -> list[tuple]:
         """A step's launches on ``perm`` (default: the epoch order), in order, as (name, arguments): ops of

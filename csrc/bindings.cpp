@@ -645,11 +645,13 @@ void wgrad_reduce(const Tensor& ws, Tensor& dw, const optional<Tensor>& db, int6
 // workgroup), per-sample vector length, flat params, largest per-rank batch the batch-staging path
 // handles, exchange words per sender, workgroups per sample of the split step, samples per tile of
 // the sample-tile kernel, smallest per-rank batch the auto mode runs on it, floats of lenet_update's split-K
-// fc scratch] (engine/fused.py LenetLayout).
+// fc scratch, lenet_update's FC tiles and CONV blocks, the float offset of the scratch's arrival counters, the
+// per-rank batch from which the engine allocates the scratch] (engine/fused.py LenetLayout).
 std::vector<int64_t> lenet_layout() {
   return {csed::lenet_wimg_elems(), csed::lenet_conv_param_count(), csed::lenet_vec_len(),
           csed::lenet_param_count(), csed::kLenetStageMaxB, csed::lenet_exch_words(),
-          csed::lenet::SPLIT_K, csed::kLenetTileSamples, csed::kLenetTileMinB, csed::lenet_fc_part_elems()};
+          csed::lenet::SPLIT_K, csed::kLenetTileSamples, csed::kLenetTileMinB, csed::lenet_fc_part_elems(),
+          csed::lenet::FC_TILES, csed::lenet::NB_CONV, csed::lenet::FC_PART_FLOATS, csed::kLenetFcPartMinB};
 }
 
 // kernels/lenet_plan.h for Python (engine/fused.py LenetPlan / LenetGeometry; integers only, so no GPU):
@@ -868,18 +870,25 @@ csed::LenetUpdateArgs update_args(const Tensor& slab, int64_t grid, const Tensor
     a.fc_part = fc_part->data_ptr<float>();
     a.fc_part_n = fc_part->numel();
   }
-  // exch_id >= 0: csrc/comm buffer of the fused gradient exchange (checked by the launcher)
-  TORCH_CHECK(exch_id < 0 || !a.grad_in, "lenet_update: the fused exchange reduces the slabs itself (no grad_in)");
+  // exch_id >= 0: csrc/comm buffer of the fused gradient exchange (resolved and checked by update_plan below)
   a.exch_id = (int)exch_id; a.exch_timeout_s = exch_timeout_s;
   // device-resident learning-rate schedule: the kernel that applies SGD picks its step's rate
   check_lr_schedule("lenet_update", params, lr_table, lr_pos);
-  TORCH_CHECK(apply_sgd || !lr_table.has_value(),
-              "lenet_update: reduce-only mode applies no SGD step and takes no lr_table");
   if (lr_table.has_value()) {
     a.lr_table = lr_table->data_ptr<float>(); a.lr_len = (int)lr_table->numel();
     a.lr_pos = lr_pos->data_ptr<int64_t>();
   }
   return a;
+}
+
+// The exchange buffer's device view (a.exch_id >= 0) and the launch's plan (kernels/lenet_plan.h): which
+// form, instantiation and grid it gets, or the rule the argument block breaks.
+csed::LenetUpdatePlan update_plan(const csed::LenetUpdateArgs& a, csed::comm::IpcPeers* px) {
+  *px = {};
+  if (a.exch_id >= 0) CHECK_HIP(csed::comm::ipc_peers(a.exch_id, px));
+  const csed::LenetUpdatePlan plan = csed::lenet_update_plan(a, *px);
+  TORCH_CHECK(!plan.error, "lenet_update: ", plan.error);
+  return plan;
 }
 
 void lenet_update(const Tensor& slab, int64_t grid, const Tensor& vslab, int64_t B, const optional<Tensor>& grad_in, const optional<Tensor>& grad_out,
@@ -894,8 +903,26 @@ void lenet_update(const Tensor& slab, int64_t grid, const Tensor& vslab, int64_t
       update_args(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
                   nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts, loss_acc, mfma_dtype, dbg,
                   exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos);
+  csed::comm::IpcPeers px;
+  update_plan(a, &px);
   CHECK_HIP(csed::launch_lenet_update(a, optpt<float>(loss_parts), (int)nparts, optpt<float>(loss_acc),
-                                      cur_stream(params)));
+                                      cur_stream(params), &px));
+}
+
+// kernels/lenet_plan.h lenet_update_plan for Python (engine/fused.py LenetUpdatePlan; integers only, so no GPU):
+// [form, world_bound, loopback, sched, blocks, fc_blocks, waves_per_tile, tiles_per_block, slices, fc_tpb, fc_sl]
+// and the rule the launch breaks ("" for a valid one).  forced_slices < 0: this process's CSED_FC_SLICES.
+std::tuple<std::vector<int64_t>, std::string> lenet_update_plan(int64_t B, bool apply_sgd, bool grad_in, bool vslab,
+                                                                int64_t exch_world, bool exch_loopback,
+                                                                int64_t exch_cap, bool exch_timeout, bool lr_table,
+                                                                bool lr_pos, bool ticket, int64_t lr_len,
+                                                                int64_t fc_part_n, int64_t forced_slices) {
+  const csed::LenetUpdatePlan p = csed::lenet_update_plan(
+      (int)B, apply_sgd, grad_in, vslab, (int)exch_world, exch_loopback, exch_cap, exch_timeout, lr_table, lr_pos,
+      ticket, (int)lr_len, fc_part_n, forced_slices < 0 ? csed::lenet_forced_fc_slices() : (int)forced_slices);
+  return {{p.form, p.world_bound, p.loopback, p.sched, p.blocks, p.fc_blocks, p.waves_per_tile, p.tiles_per_block,
+           p.slices, p.fc_tpb, p.fc_sl},
+          p.error ? p.error : ""};
 }
 
 void lenet_eval(const Tensor& images, const Tensor& labels, const Tensor& order, int64_t n, const Tensor& wimg,
@@ -1027,14 +1054,17 @@ struct LenetStepper : torch::CustomClassHolder {
                   int64_t exch_id, double exch_timeout_s, double grad_post, optional<Tensor> fc_part,
                   optional<Tensor> lr_table, optional<Tensor> lr_pos) {
     TORCH_CHECK(apply_sgd && !grad_in && !grad_out && cursor, "LenetStepper: set_update takes a full step at a cursor");
-    ua = update_args(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
-                     nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts_t, loss_acc_t, mfma_dtype, dbg,
-                     exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos);
+    const csed::LenetUpdateArgs a =
+        update_args(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
+                    nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts_t, loss_acc_t, mfma_dtype, dbg,
+                    exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos);
+    csed::comm::IpcPeers peers;
+    update_plan(a, &peers);  // the exchange's view and the plan's error once, here: a bad block never reaches run()
+    ua = a;
+    px = peers;
     loss_parts = optpt<float>(loss_parts_t);
     loss_acc = optpt<float>(loss_acc_t);
     nparts = nparts_;
-    px = {};
-    if (exch_id >= 0) CHECK_HIP(csed::comm::ipc_peers((int)exch_id, &px));  // once, not per launch
     keep_u = {slab,   vslab,      params,       momentum,   wimg, step,   ticket,
               cursor, rng_offset, loss_parts_t, loss_acc_t, dbg,  fc_part, lr_table, lr_pos};
   }
@@ -1071,6 +1101,9 @@ TORCH_LIBRARY(csed, m) {
   m.def("lenet_plan(int B, int grid, int mfma_dtype, int kernel, bool staged, bool stage_next, bool cursor, bool train) "
         "-> (int[], str)", &lenet_plan);
   m.def("lenet_geometry(int B, int mfma_dtype, int grid, bool allow_split) -> int[]", &lenet_geometry);
+  m.def("lenet_update_plan(int B, bool apply_sgd, bool grad_in, bool vslab, int exch_world, bool exch_loopback, "
+        "int exch_cap, bool exch_timeout, bool lr_table, bool lr_pos, bool ticket, int lr_len, int fc_part_n, "
+        "int forced_slices) -> (int[], str)", &lenet_update_plan);
   m.def("lenet_tile_grid(int B) -> int", [](int64_t B) { return (int64_t)csed::lenet_tile_grid((int)B); });
   m.def("conv2d_wgrad_workspace(int N, int IC, int KH, int KW, int OC) -> int",
         [](int64_t N, int64_t IC, int64_t KH, int64_t KW, int64_t OC) {

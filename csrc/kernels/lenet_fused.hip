@@ -1,17 +1,22 @@
 // Fused LeNet (ref src/model.py:4-22) training step for gfx950.
 //
-// One workgroup (512 threads = 8 waves, two per SIMD) owns whole samples: it
-// gathers the raw uint8 image, normalises it, runs conv1 -> pool -> relu ->
-// conv2 -> Dropout2d -> pool -> relu -> fc1 -> relu -> dropout -> fc2 ->
-// log_softmax -> NLL, and the complete backward pass, with every activation
-// resident in LDS.  The only global traffic per sample is the 784-byte image;
-// per workgroup it is the 33 KB of conv weight images (to LDS), the fc1
-// fragments (to registers, reused across samples) and the partial gradient
-// (21,840 fp32) written once to a slab.  A second kernel (lenet_update)
-// reduces the slabs in a fixed order, applies SGD with momentum, refreshes
-// the 16-bit weight images and bumps the device step/cursor/RNG counters, so
-// a training step is exactly two launches (plus one RCCL all-reduce between
-// them for DDP).
+// One workgroup (1024 threads = 16 waves, four per SIMD) owns whole samples
+// (or, in the split step, SPLIT_K workgroups share one): it takes the raw uint8
+// image (staged one step ahead, or gathered through the permutation),
+// normalises it, runs conv1 -> pool -> relu -> conv2 -> Dropout2d -> pool ->
+// relu -> fc1 -> relu -> dropout -> fc2 -> log_softmax -> NLL, and the complete
+// backward pass, with every activation resident in LDS.  The only global
+// traffic per sample is the 784-byte image; per workgroup it is the 72 KB
+// weight image (W2C | W2D | F1, copied to LDS by LDS-DMA), 590 fp32 biases and
+// fc2 weights, the conv1 weights and the label.  The outputs are a 5,376-float
+// partial conv gradient per workgroup (the slab: CNP_PAD, kernels/lenet_layout.h) and a 464-float vector of fc
+// activations / gradients per sample (the vector slab).  A second kernel
+// (lenet_update) reduces the slabs in a fixed order, forms the fc gradients
+// from the vectors on the fp32 MFMA, applies SGD with momentum, refreshes the
+// 16-bit weight images and bumps the device step/cursor/RNG counters, so a
+// training step is exactly two launches (the data-parallel exchange runs inside
+// the second, or as one all-reduce between its two halves).  Which kernel,
+// instantiation and grid a launch gets: kernels/lenet_plan.h.
 //
 // Matrix work runs on v_mfma_f32_16x16x32_{bf16,f16}:
 //   conv1 fwd   : [576 px x 25] . [25 x 10]        36 tiles, 1 K-step
@@ -1349,36 +1354,11 @@ __global__ void lenet_pack_kernel(const float* __restrict__ params, unsigned sho
 //
 // Reductions run in a fixed order everywhere: bitwise reproducible.
 // ---------------------------------------------------------------------------
-constexpr int NB_CONV = N_CHUNKS;                   // 84: one 64-slot slab chunk per block half
+// (NB_CONV, FC_TILES, fc_waves_per_tile / fc_tiles_per_block / fc_blocks / update_blocks, NB_UPDATE and
+// FC_PART_FLOATS: kernels/lenet_plan.h, next to the launch plan that is built from them)
+static_assert(NB_CONV == N_CHUNKS, "one 64-slot slab chunk per CONV block half");
 static_assert(UP_C * 4 == 64, "a CONV block half reduces one 64-slot slab chunk");
-constexpr int FC1_TILES = 4 * 21, FC_TILES = FC1_TILES + 4;
-// FC role: wpt waves per tile (K split over them), 8 / wpt tiles per block.  A
-// small batch uses one wave per tile (no combine, no barrier: the tile's K is one
-// or two 64-sample chunks); a large batch streams K over 8 waves.
-__host__ __device__ constexpr int fc_waves_per_tile(int B) {
-  return B <= 128 ? 1 : (B <= 256 ? 2 : (B <= 512 ? 4 : 8));
-}
-// Update workgroups of UP_NT threads: a CONV workgroup holds one 64-parameter block; an FC
-// workgroup UP_NT/64/wpt tiles when the batch splits K over waves, else ONE tile: the FC
-// phase is bound by per-CU load / store issue (32 loads and ~12 stores per tile wave), so
-// 88 workgroups of one tile beat 11 of eight (16.86 -> 16.38 us/step, round 1).
-__host__ __device__ constexpr int fc_tiles_per_block(int B) {
-  return fc_waves_per_tile(B) == 1 ? 1 : UP_NT / 64 / fc_waves_per_tile(B);
-}
-__host__ __device__ constexpr int fc_blocks(int B) {
-  return (FC_TILES + fc_tiles_per_block(B) - 1) / fc_tiles_per_block(B);
-}
-__host__ __device__ constexpr int update_blocks(int B) { return fc_blocks(B) + NB_CONV; }
-// (update_role shifts by log2 of both: they must stay powers of two)
-__host__ __device__ constexpr bool fc_shapes_pow2() {
-  for (int B : {1, 32, 64, 128, 129, 256, 257, 512, 513, 1024, 8192}) {
-    const int w = fc_waves_per_tile(B), t = fc_tiles_per_block(B);
-    if ((w & (w - 1)) || (t & (t - 1))) return false;
-  }
-  return true;
-}
-static_assert(fc_shapes_pow2(), "fc waves per tile / tiles per block: powers of two");
-constexpr int NB_FC = FC_TILES;                     // FC blocks at most (one tile each)
+static_assert(UP_NT == 64 * UP_WAVES && SGD_BLOCKS == (NP + 255) / 256, "lenet_plan.h: update workgroup, SGD grid");
 // FC tile of workgroup b (one tile per workgroup): b = 8 * slot + xcd takes position
 // 11 * xcd + slot of the fc1 tiles in column-block-major order (q -> row block q % 4, column
 // block q / 4), then the 4 fc2 tiles.  A bijection on [0, 88): see the static_assert below.
@@ -1396,10 +1376,6 @@ __host__ __device__ constexpr bool fc_tile_map_is_bijective() {
   return true;
 }
 static_assert(FC_TILES % 8 == 0 && fc_tile_map_is_bijective(), "FC tile map");
-constexpr int NB_UPDATE = NB_CONV + NB_FC;
-// split-K fc gradients (fc_split_slices): at most 8 slices of 88 tiles x 256 partial sums, then
-// 88 arrival counters (ints, zero between launches) in the same fp32 scratch
-constexpr int FC_PART_FLOATS = 8 * FC_TILES * 256;
 
 __device__ __forceinline__ void add4(float4& a, const float4& b) {
   a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
@@ -1524,7 +1500,7 @@ __device__ __forceinline__ void finish_param4(const LenetUpdateArgs& a, int i, f
 // are 512-byte contiguous runs.  Every wait is bounded by a wall-clock timeout
 // that raises the comm error word instead of hanging the GPU.
 // ---------------------------------------------------------------------------
-constexpr int EXCH_WORDS = CNP_PAD + FC_TILES * 256;  // 27904
+static_assert(EXCH_WORDS == CNP_PAD + FC_TILES * 256, "lenet_plan.h: the exchange words (27904)");
 
 __device__ __forceinline__ uint64_t ll_word(float v, uint32_t t) {
   return ((uint64_t)t << 32) | (uint64_t)__float_as_uint(v);
@@ -2425,100 +2401,62 @@ hipError_t launch_lenet_train(const LenetTrainArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// Batch slices of the split-K fc gradients for a launch (1: unsplit).  Large batches only (the
-// FC role's K loop then streams B x 32 features per tile on 88 CUs), no exchange, no grad_in,
-// scratch of FC_PART_FLOATS + FC_TILES (the partials, then the zeroed per-tile counters).  Auto: S = B / 1024 rounded down to a power of two, at most 8;
-// CSED_FC_SLICES = 1 / 2 / 4 / 8 forces it (A/B measurements).
-static int fc_split_slices(const LenetUpdateArgs& a) {
-  if (!a.fc_part || a.exch_id >= 0 || a.grad_in || a.B <= 512) return 1;
+// CSED_FC_SLICES = 1 / 2 / 4 / 8 forces the split-K slice count (A/B measurements); 0: automatic.  Read
+// once per process, here and nowhere else: the plan takes it as an argument.
+int lenet_forced_fc_slices() {
   static const int forced = [] {
     const char* e = std::getenv("CSED_FC_SLICES");
     return e ? std::atoi(e) : 0;
   }();
-  int S = 1;
-  if (forced > 0) {
-    while (S * 2 <= std::min(forced, 8)) S *= 2;
-  } else {
-    while (S * 2 <= 8 && S * 2 * 1024 <= a.B) S *= 2;
-  }
-  if (a.fc_part_n < FC_PART_FLOATS + FC_TILES) return 1;  // partials + the per-tile counters
-  return S;
+  return forced;
 }
 
+// Runs what lenet_update_plan (kernels/lenet_plan.h) decides: lenet_sgd_kernel on grad_in, or
+// lenet_update_kernel in the plan's (XW, LBC, SCHED) instantiation, on its grid, with its trailing arguments.
 hipError_t launch_lenet_update(const LenetUpdateArgs& a, float* loss_parts, int nparts, float* loss_acc,
                                hipStream_t s, const comm::IpcPeers* px_cached) {
-  // a device-resident schedule: SGD-applying launches only, with a position and at least one entry
-  const bool sched = a.lr_table != nullptr;
-  if (sched && (!a.apply_sgd || !a.lr_pos || a.lr_len < 1 || !a.ticket)) return hipErrorInvalidValue;
-  if (a.apply_sgd && a.grad_in) {
-    CSED_DISPATCH_UPDATE(a.mfma_dtype, {
-      if (sched) hipLaunchKernelGGL((lenet_sgd_kernel<scalar_t, true>), dim3(cdiv(NP, 256)), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((lenet_sgd_kernel<scalar_t, false>), dim3(cdiv(NP, 256)), dim3(256), 0, s, a);
-    });
-    return hipGetLastError();
-  }
-  if (!a.vslab || a.B <= 0) return hipErrorInvalidValue;
+  static_assert(NB_UPDATE <= comm::kIpcMaxBlocks, "one exchange counter per update workgroup");
   comm::IpcPeers px{};
   if (a.exch_id >= 0) {
-    // fused data-parallel exchange: the buffer must hold this kernel's word layout.  The
-    // exchange tag is a per-workgroup call counter, so the workgroup -> exchange-word map
-    // must not depend on the batch: one FC tile per workgroup (NB_UPDATE workgroups) for
-    // every B, the full steps' and the epoch tail's alike (a batch-dependent layout let
-    // the counters of different words drift apart between steps of different batch sizes).
-    static_assert(NB_UPDATE <= comm::kIpcMaxBlocks, "one exchange counter per update workgroup");
-    if (px_cached) {  // resolved once by the caller (csrc/bindings.cpp LenetStepper)
+    if (px_cached) {  // resolved once by the caller (csrc/bindings.cpp)
       px = *px_cached;
     } else {
       const hipError_t e = comm::ipc_peers(a.exch_id, &px);
       if (e != hipSuccess) return e;
     }
-    if (px.cap < EXCH_WORDS || a.exch_timeout_s <= 0.0) return hipErrorInvalidValue;
-    const uint64_t ticks = (uint64_t)(a.exch_timeout_s * 1e8);  // s_memrealtime: 100 MHz
-    // (px.loopback: the looped-back exchange with its invariant check, own instantiations)
-#define CSED_UPDATE_XS(W, L, S)                                                                               \
-  hipLaunchKernelGGL((lenet_update_kernel<scalar_t, W, L, S>), dim3(NB_UPDATE), dim3(UP_NT), 0, s, a, a.vslab, a.B, \
-                     loss_parts, nparts, loss_acc, ticks, 1, 1, px)
-#define CSED_UPDATE_X(W, L)                \
-  do {                                     \
-    if (sched) CSED_UPDATE_XS(W, L, true); \
-    else CSED_UPDATE_XS(W, L, false);      \
-  } while (0)
-    CSED_DISPATCH_UPDATE(a.mfma_dtype, {
-      if (px.loopback) {
-        if (px.world <= 2) CSED_UPDATE_X(2, true);
-        else if (px.world <= 4) CSED_UPDATE_X(4, true);
-        else CSED_UPDATE_X(8, true);
-      } else {
-        if (px.world <= 2) CSED_UPDATE_X(2, false);
-        else if (px.world <= 4) CSED_UPDATE_X(4, false);
-        else CSED_UPDATE_X(8, false);
-      }
-    });
-#undef CSED_UPDATE_X
-#undef CSED_UPDATE_XS
-    return hipGetLastError();
   }
-  const int S = fc_split_slices(a);
-  if (S > 1) {  // split-K fc gradients: one tile per workgroup x S slices (the last one finishes)
+  const LenetUpdatePlan p = lenet_update_plan(a, px);
+  if (p.error) return hipErrorInvalidValue;
+  if (p.form == kUpdateSgd) {
     CSED_DISPATCH_UPDATE(a.mfma_dtype, {
-      if (sched)
-        hipLaunchKernelGGL((lenet_update_kernel<scalar_t, 0, false, true>), dim3(FC_TILES * S + NB_CONV), dim3(UP_NT),
-                           0, s, a, a.vslab, a.B, loss_parts, nparts, loss_acc, (uint64_t)0, 1, S, px);
-      else
-        hipLaunchKernelGGL((lenet_update_kernel<scalar_t, 0>), dim3(FC_TILES * S + NB_CONV), dim3(UP_NT), 0, s, a,
-                           a.vslab, a.B, loss_parts, nparts, loss_acc, (uint64_t)0, 1, S, px);
+      void (*kern)(LenetUpdateArgs) = p.sched ? lenet_sgd_kernel<scalar_t, true> : lenet_sgd_kernel<scalar_t, false>;
+      hipLaunchKernelGGL(kern, dim3(p.blocks), dim3(256), 0, s, a);
     });
     return hipGetLastError();
   }
-  const int nblocks = update_blocks(a.B);
-  CSED_DISPATCH_UPDATE(a.mfma_dtype, {
-    if (sched)
-      hipLaunchKernelGGL((lenet_update_kernel<scalar_t, 0, false, true>), dim3(nblocks), dim3(UP_NT), 0, s, a,
-                         a.vslab, a.B, loss_parts, nparts, loss_acc, (uint64_t)0, 0, 1, px);
-    else
-      hipLaunchKernelGGL((lenet_update_kernel<scalar_t, 0>), dim3(nblocks), dim3(UP_NT), 0, s, a, a.vslab,
-                         a.B, loss_parts, nparts, loss_acc, (uint64_t)0, 0, 1, px);
-  });
+  const uint64_t ticks = p.form == kUpdateExchange ? (uint64_t)(a.exch_timeout_s * 1e8) : 0;  // s_memrealtime: 100 MHz
+  // The (XW, LBC, SCHED) instantiations that occur: the exchange's world bound 2 / 4 / 8, looped back (its
+  // invariant check) or not, and XW = 0 without one; each with and without the schedule.
+  void (*kern)(LenetUpdateArgs, const float*, int, float*, int, float*, uint64_t, int, int, comm::IpcPeers) = nullptr;
+#define CSED_UPDATE_PICK(W, L)               \
+  if (p.world_bound == W && p.loopback == L) \
+  kern = p.sched ? lenet_update_kernel<scalar_t, W, L, true> : lenet_update_kernel<scalar_t, W, L, false>
+  if (p.world_bound) {
+    CSED_DISPATCH_UPDATE(a.mfma_dtype, {
+      CSED_UPDATE_PICK(2, true);
+      CSED_UPDATE_PICK(4, true);
+      CSED_UPDATE_PICK(8, true);
+      CSED_UPDATE_PICK(2, false);
+      CSED_UPDATE_PICK(4, false);
+      CSED_UPDATE_PICK(8, false);
+    });
+  } else {
+    CSED_DISPATCH_UPDATE(a.mfma_dtype, { CSED_UPDATE_PICK(0, false); });
+  }
+#undef CSED_UPDATE_PICK
+  if (!kern) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kern, dim3(p.blocks), dim3(UP_NT), 0, s, a, a.vslab, a.B, loss_parts, nparts, loss_acc, ticks,
+                     p.fc_tpb, p.fc_sl, px);
   return hipGetLastError();
 }
 

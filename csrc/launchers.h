@@ -308,9 +308,19 @@ struct LenetUpdateArgs {
   const float* lr_table; int lr_len; int64_t* lr_pos;
 };
 int64_t lenet_exch_words();
+int lenet_forced_fc_slices();  // CSED_FC_SLICES (0: automatic), read once per process
+// The plan of a launch with these arguments (kernels/lenet_plan.h); px: the exchange's view where a.exch_id >= 0.
+inline LenetUpdatePlan lenet_update_plan(const LenetUpdateArgs& a, const comm::IpcPeers& px) {
+  const bool exch = a.exch_id >= 0;
+  return lenet_update_plan(a.B, a.apply_sgd != 0, a.grad_in != nullptr, a.vslab != nullptr,
+                           exch ? (px.world > 1 ? px.world : 1) : 0, exch && px.loopback != 0, exch ? px.cap : 0,
+                           a.exch_timeout_s > 0.0, a.lr_table != nullptr, a.lr_pos != nullptr, a.ticket != nullptr,
+                           a.lr_len, a.fc_part ? a.fc_part_n : 0, lenet_forced_fc_slices());
+}
+// Runs what the plan decides (hipErrorInvalidValue where it has an error).
 // loss_parts [nparts, 2] are summed in a fixed order into loss_acc[2] (optional).
-// px: the exchange buffer's device view resolved once by the caller (csrc/bindings.cpp
-// LenetStepper), so a launch does no registry lookup; null: looked up from a.exch_id.
+// px: the exchange buffer's device view resolved once by the caller (csrc/bindings.cpp),
+// so a launch does no registry lookup; null: looked up from a.exch_id.
 hipError_t launch_lenet_update(const LenetUpdateArgs& a, float* loss_parts, int nparts, float* loss_acc,
                                hipStream_t s, const comm::IpcPeers* px = nullptr);
 hipError_t launch_lenet_pack(const float* params, uint16_t* wimg, int mfma_dtype, hipStream_t s);

@@ -1,8 +1,9 @@
 // Host-side check of the fused launches' plan (csrc/kernels/lenet_plan.h), built with AddressSanitizer +
 // UndefinedBehaviorSanitizer on the host (tests/test_native_host_cpu.py): (a) every plan the resolver calls
 // valid keeps the invariants the kernels' instantiations rely on, over every batch / grid / dtype / request /
-// staging / train-or-eval combination near the thresholds, and (b) the engine's default geometry at each
-// threshold is the hand-written table below.
+// staging / train-or-eval combination near the thresholds, (b) the engine's default geometry at each
+// threshold is the hand-written table below, and (c) lenet_update's plan is, case by case, what the launcher
+// decided before the plan existed (transcribed below), with the grid invariants update_role relies on.
 #include <cstdio>
 #include <initializer_list>
 
@@ -48,6 +49,120 @@ static long check_batch(int B) {
   return valid;
 }
 
+// ---- lenet_update.  The oracle: a literal transcription of launch_lenet_update, fc_split_slices and
+// update_blocks as they stood in lenet_fused.hip before the plan (numbers written out, nothing from the header).
+struct OldUpdate {
+  bool error;
+  int form, xw, loopback, blocks, fc_tpb, fc_sl;  // the kernel launched, its grid and two trailing arguments
+};
+static int old_waves_per_tile(int B) { return B <= 128 ? 1 : (B <= 256 ? 2 : (B <= 512 ? 4 : 8)); }
+static int old_tiles_per_block(int B) { return old_waves_per_tile(B) == 1 ? 1 : 512 / 64 / old_waves_per_tile(B); }
+static int old_fc_blocks(int B) { return (88 + old_tiles_per_block(B) - 1) / old_tiles_per_block(B); }
+static int old_update_blocks(int B) { return old_fc_blocks(B) + 84; }
+static int old_fc_split_slices(bool fc_part, bool exch, bool grad_in, int B, long fc_part_n, int forced) {
+  if (!fc_part || exch || grad_in || B <= 512) return 1;
+  int S = 1;
+  if (forced > 0) {
+    while (S * 2 <= (forced < 8 ? forced : 8)) S *= 2;
+  } else {
+    while (S * 2 <= 8 && S * 2 * 1024 <= B) S *= 2;
+  }
+  if (fc_part_n < 8 * 88 * 256 + 88) return 1;
+  return S;
+}
+static OldUpdate old_launch_update(int B, bool apply_sgd, bool grad_in, bool vslab, int world, bool loopback, long cap,
+                                   double timeout_s, bool lr_table, bool lr_pos, bool ticket, int lr_len,
+                                   long fc_part_n, int forced) {
+  const OldUpdate invalid{true, 0, 0, 0, 0, 0, 0};
+  const bool sched = lr_table, exch = world > 0;
+  if (sched && (!apply_sgd || !lr_pos || lr_len < 1 || !ticket)) return invalid;
+  if (apply_sgd && grad_in) return {false, kUpdateSgd, 0, 0, (21840 + 255) / 256, 0, 0};
+  if (!vslab || B <= 0) return invalid;
+  if (exch) {
+    if (cap < 27904 || timeout_s <= 0.0) return invalid;
+    return {false, kUpdateExchange, world <= 2 ? 2 : (world <= 4 ? 4 : 8), loopback, 84 + 88, 1, 1};
+  }
+  const int S = old_fc_split_slices(fc_part_n > 0, exch, grad_in, B, fc_part_n, forced);
+  if (S > 1) return {false, kUpdateSplitK, 0, 0, 88 * S + 84, 1, S};
+  return {false, kUpdatePlain, 0, 0, old_update_blocks(B), 0, 1};
+}
+
+static bool pow2(int v) { return v > 0 && !(v & (v - 1)); }
+
+// defect: 0 none; 1 no lr_pos, 2 empty table, 3 no ticket (scheduled launches); 4 no vslab, 5 batch 0;
+// 6 exchange buffer one word short, 7 exchange timeout 0
+static long check_update(int B, int mode, int world, bool loopback, bool sched, long fc_part_n, int forced, int defect) {
+  const bool apply_sgd = mode != 1, grad_in = mode == 2;  // step, reduce, apply
+  const bool lr_pos = sched && defect != 1, ticket = defect != 3, vslab = defect != 4;
+  const int lr_len = sched ? (defect == 2 ? 0 : 3) : 0, batch = defect == 5 ? 0 : B;
+  const long cap = world ? (defect == 6 ? 27903 : 27904) : 0;
+  const double timeout_s = defect == 7 ? 0.0 : 2.0;
+  const LenetUpdatePlan p = lenet_update_plan(batch, apply_sgd, grad_in, vslab, world, loopback, cap, timeout_s > 0.0,
+                                              sched, lr_pos, ticket, lr_len, fc_part_n, forced);
+  const OldUpdate o = old_launch_update(batch, apply_sgd, grad_in, vslab, world, loopback, cap, timeout_s, sched,
+                                        lr_pos, ticket, lr_len, fc_part_n, forced);
+#define WHERE                                                                                                      \
+  "update B=%d mode=%d world=%d loopback=%d sched=%d scratch=%ld forced=%d defect=%d", B, mode, world, loopback, sched, \
+      fc_part_n, forced, defect
+  if (world && grad_in) {  // (the op refused this before it reached the launcher; the plan says so itself)
+    EXPECT(p.error && p.error[0], WHERE);
+    return 0;
+  }
+  EXPECT((p.error != nullptr) == o.error, WHERE);
+  EXPECT(!p.error || p.error[0], WHERE);  // every rejected launch carries a sentence
+  if (p.error || o.error) return 0;
+  EXPECT(p.form == o.form && p.world_bound == o.xw && p.loopback == (o.loopback != 0) && p.sched == sched, WHERE);
+  EXPECT(p.blocks == o.blocks && p.fc_tpb == o.fc_tpb && p.fc_sl == o.fc_sl, WHERE);
+  if (p.form == kUpdateSgd) return 1;
+  EXPECT(p.slices == p.fc_sl && (p.slices > 1) == (p.form == kUpdateSplitK), WHERE);
+  EXPECT(p.blocks == (p.form == kUpdateSplitK ? 88 * p.slices + 84 : p.fc_blocks + 84), WHERE);
+  EXPECT(p.blocks == p.fc_blocks + 84, WHERE);
+  EXPECT(pow2(p.waves_per_tile) && pow2(p.tiles_per_block) && pow2(p.slices) && p.slices <= 8, WHERE);
+  EXPECT(p.waves_per_tile == old_waves_per_tile(B), WHERE);
+  // the kernel packs 8 / waves_per_tile tiles into a block where it derives them from B (fc_tpb 0); where the
+  // launcher fixes one tile per block (the exchange's batch-independent map, split-K) the other waves idle
+  if (p.fc_tpb == 0) {
+    EXPECT(p.waves_per_tile == 1 ? p.tiles_per_block == 1 : p.waves_per_tile * p.tiles_per_block == 8, WHERE);
+    EXPECT(p.fc_blocks == (88 + p.tiles_per_block - 1) / p.tiles_per_block, WHERE);
+  } else {
+    EXPECT(p.tiles_per_block == 1 && p.waves_per_tile * p.tiles_per_block <= 8 && p.fc_blocks == 88 * p.slices, WHERE);
+  }
+  EXPECT(p.form != kUpdateExchange || (p.blocks == 172 && pow2(p.world_bound) && p.world_bound >= world), WHERE);
+  EXPECT(p.form != kUpdateSplitK || (B > 512 && !world && fc_part_n >= 8 * 88 * 256 + 88), WHERE);
+#undef WHERE
+  return 1;
+}
+
+static long check_updates() {
+  long valid = 0;
+  const long need = 8 * 88 * 256 + 88;
+  for (int B : {1, 8, 32, 33, 128, 129, 256, 257, 512, 513, 1024, 1025, 2047, 2048, 2051, 4096, 8192, 16384})
+    for (int mode = 0; mode < 3; ++mode)
+      for (int world : {0, 2, 3, 4, 8})
+        for (int loopback = 0; loopback <= 1; ++loopback)
+          for (int sched = 0; sched <= 1; ++sched)
+            for (long scratch : {0L, need - 1, need})
+              for (int forced : {0, 1, 2, 3, 8, 9})
+                for (int defect = 0; defect < 8; ++defect)
+                  valid += check_update(B, mode, world, loopback, sched, scratch, forced, defect);
+  // the corner cases by hand
+  auto slices = [&](int B, long scratch, int forced) {
+    return lenet_update_plan(B, true, false, true, 0, false, 0, true, false, false, true, 0, scratch, forced).slices;
+  };
+  EXPECT(slices(2047, need, 0) == 1 && slices(2048, need, 0) == 2 && slices(4096, need, 0) == 4, "automatic slices");
+  EXPECT(slices(8192, need, 0) == 8 && slices(16384, need, 0) == 8, "automatic slices: at most 8");
+  EXPECT(slices(512, need, 8) == 1 && slices(513, need, 8) == 8, "a forced count applies past B = 512");
+  EXPECT(slices(513, need, 3) == 2 && slices(513, need, 9) == 8 && slices(8192, need, 1) == 1, "forced: pow2, <= 8");
+  EXPECT(slices(8192, need - 1, 0) == 1 && slices(8192, 0, 0) == 1, "a short scratch runs unsplit, no error");
+  EXPECT(!lenet_update_plan(8192, true, false, true, 0, false, 0, true, false, false, true, 0, need - 1, 0).error,
+         "a short scratch is no error");
+  const LenetUpdatePlan x = lenet_update_plan(8192, true, false, true, 2, true, 27904, true, false, false, true, 0, need, 0);
+  EXPECT(x.blocks == 172 && x.fc_blocks == 88 && x.tiles_per_block == 1 && x.slices == 1 && x.loopback, "exchange at 8192");
+  EXPECT(lenet_update_plan(2051, true, false, true, 0, false, 0, true, false, false, true, 0, need, 0).blocks == 260,
+         "B = 2051: two slices, 260 blocks");
+  return valid;
+}
+
 struct Row {
   int dtype, B;                                  // default grid, split allowed
   int grid, split, staged, tile_staged, rows;    // the geometry
@@ -59,6 +174,8 @@ int main() {
   for (int B = 1; B <= 1100; ++B) valid += check_batch(B);
   for (int B : {2048, 2051, 4096, 8192}) valid += check_batch(B);
   EXPECT(valid > 1000000, "only %ld valid plans", valid);
+  const long updates = check_updates();
+  EXPECT(updates > 20000, "only %ld valid update plans", updates);
 
   // launches that must stay rejected, each with a message
   EXPECT(lenet_plan(64, 64, kBF16, 2, false, false, false, true, true).error, "kernel 2 off the tile grid");

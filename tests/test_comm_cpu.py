@@ -61,7 +61,8 @@ def test_exchange_buffer_layout():
     conv_pad, nparams, words = layout.conv_params, layout.n_params, layout.exch_words
     assert nparams == 21840 and conv_pad == 5376 and layout.split_k == 4  # split step: 4 workgroups / sample
     # sample tiles of 4 from batch 1024
-    assert len(layout) == 10 and layout.tile_samples == 4 and layout.tile_min_batch == 1024
+    assert len(layout) == 14 and layout.tile_samples == 4 and layout.tile_min_batch == 1024
     fc_tiles = 4 * 21 + 4  # fc1: 4 x 21 tiles of [dW1 | db1], fc2: 4 tiles of [dW2 | db2]
+    assert layout.fc_tiles == fc_tiles and layout.conv_blocks == conv_pad // 64
     assert words == conv_pad + fc_tiles * 256 == 27904
     assert words % 4 == 0  # the IPC buffers are allocated in multiples of 4 words

@@ -40,7 +40,30 @@ def test_plan_and_geometry_name_every_value(schemas):
     assert tuple(fused.lenet_geometry(8, 1)) == tuple(int(v) for v in geo) == (32, 1, 1, 0, 32)
     lay = fused.lenet_layout()
     assert lay.vec_len == 464 and lay.fc_part_elems == 8 * 88 * 256 + 88
+    assert (lay.fc_tiles, lay.conv_blocks, lay.fc_counters_off, lay.fc_part_min_batch) == (88, 84, 8 * 88 * 256, 1025)
     assert [fused.tile_grid(B) for B in (1, 4, 5, 1023, 1024, 8192)] == [1, 1, 2, 256, 256, 256]
+
+
+def test_update_plan_names_every_value(schemas):
+    """LenetUpdatePlan: one field per value of csed::lenet_update_plan (its integers, then the message), the
+    wrapper returns exactly those values, and a bad combination carries the plan's sentence -- the one
+    csed::lenet_update raises.  No GPU: integer arguments only."""
+    lay = fused.lenet_layout()
+    raw = (2051, True, False, True, 0, False, 0, True, False, False, True, 0, lay.fc_part_elems, 0)
+    values, error = torch.ops.csed.lenet_update_plan(*raw)
+    assert len(fused.LenetUpdatePlan._fields) == len(values) + 1
+    plan = fused.lenet_update_plan(2051, fc_part_n=lay.fc_part_elems, forced_slices=0)
+    assert tuple(plan) == (*(int(v) for v in values), error) \
+        == (fused.UPDATE_SPLIT_K, 0, 0, 0, 260, 176, 8, 1, 2, 1, 2, "")
+    assert tuple(fused.lenet_update_plan(257, forced_slices=0)) == (fused.UPDATE_PLAIN, 0, 0, 0, 44 + 84, 44, 4, 2, 1, 0, 1, "")
+    loop = fused.lenet_update_plan(8, exch_world=2, exch_loopback=True, lr_table=True)
+    assert (loop.form, loop.world_bound, loop.loopback, loop.sched, loop.blocks) == (fused.UPDATE_EXCHANGE, 2, 1, 1, 172)
+    assert fused.lenet_update_plan(8, apply_sgd=True, grad_in=True).form == fused.UPDATE_SGD
+    assert "reduce-only mode applies no SGD step and takes no lr_table" in \
+        fused.lenet_update_plan(8, apply_sgd=False, lr_table=True).error
+    assert "the fused exchange reduces the slabs itself (no grad_in)" in \
+        fused.lenet_update_plan(8, grad_in=True, exch_world=2).error
+    assert "words per sender" in fused.lenet_update_plan(8, exch_world=2, exch_cap=lay.exch_words - 1).error
 
 
 @pytest.mark.parametrize("shape", [(1, 5, 5, 10), (10, 5, 5, 20)])

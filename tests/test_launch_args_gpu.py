@@ -6,7 +6,8 @@ import pytest
 import torch
 
 from csed_514_project_distributed_training_using_pytorch_amd.data import synthetic_mnist
-from csed_514_project_distributed_training_using_pytorch_amd.engine.fused import FusedLeNetTrainer
+from csed_514_project_distributed_training_using_pytorch_amd.engine.fused import (
+    UPDATE_EXCHANGE, UPDATE_PLAIN, UPDATE_SPLIT_K, FusedLeNetTrainer, lenet_layout)
 from csed_514_project_distributed_training_using_pytorch_amd.models import Net
 
 pytestmark = pytest.mark.gpu
@@ -79,6 +80,72 @@ def test_engine_geometry_at_the_plan_boundaries(dtype, B):
     assert eng.uses_tile_kernel() is tile and eng.kernel_names == kernel + " + lenet_update"
     assert (eng.train_args().xstage is not None) == (rows > 0)
     _eager_and_stepper_agree(eng, 2 * B)
+    eng.close()
+
+
+def _bare_engine(B, grid, **kw):
+    """An engine whose training kernels never run (zero images): lenet_update alone, on filled slabs."""
+    from csed_514_project_distributed_training_using_pytorch_amd.data.mnist import MNISTData
+
+    data = MNISTData(torch.zeros((B, 28, 28), dtype=torch.uint8), torch.zeros(B, dtype=torch.long), True)
+    torch.manual_seed(1)
+    return FusedLeNetTrainer(Net().to("cuda:0"), data, global_batch=B, grid=grid, **kw)
+
+
+def _stamped_update(eng, B, grid):
+    """One "step" update at per-rank batch B on integer slabs (csed::lenet_selftest_fill) with the block stamps
+    on, checked against its plan.  Every block stamps slot 0 at the top of update_role, so the stamped rows are
+    the blocks that ran.  The stamps carry no role, so the FC / CONV boundary is checked through the work: from a
+    zero momentum buffer the step leaves the gradient there, and a grid whose first plan.fc_blocks blocks were not
+    exactly the FC role would leave FC tiles or conv slab chunks (whole runs of parameters) unfinished."""
+    ops = torch.ops.csed
+    args = eng.update_args("step", B=B, grid=grid, dbg=torch.zeros(1024, 8, dtype=torch.long, device=eng.device))
+    plan = eng.update_plan(args)
+    assert not plan.error
+    ops.lenet_selftest_fill(eng.slab, eng.vslab, B, eng.mfma, 977 + B)
+    eng.momentum_buf.zero_()
+    ops.lenet_update(*args)
+    torch.cuda.synchronize()
+    ran = (args.dbg[:, 0] != 0).cpu()
+    assert int(ran.sum()) == plan.blocks and bool(ran[:plan.blocks].all())
+    assert bool((args.dbg[:plan.blocks, 4] != 0).all())  # each of them got to its end
+    lay = lenet_layout()
+    assert plan.blocks - plan.fc_blocks == lay.conv_blocks
+    assert plan.fc_blocks == plan.slices * -(-lay.fc_tiles // plan.tiles_per_block)
+    assert torch.isfinite(eng.momentum_buf).all()
+    assert bool((eng.momentum_buf.view(-1, 16) != 0).any(dim=1).all()), "a run of 16 parameters got no gradient"
+    return plan
+
+
+def test_update_launcher_follows_its_plan():
+    """The grid csed::lenet_update launches is csed::lenet_update_plan's (csrc/kernels/lenet_plan.h), at one
+    batch per waves-per-tile class, at two split-K slices and through a loopback exchange of world 2."""
+    eng = _bare_engine(513, 64)
+    assert eng.fc_part is None
+    want = {8: (1, 1, 88), 33: (1, 1, 88), 129: (2, 4, 22), 257: (4, 2, 44), 513: (8, 1, 88)}
+    for B, (wpt, tpb, nfc) in want.items():
+        plan = _stamped_update(eng, B, min(B, 64))
+        assert (plan.form, plan.waves_per_tile, plan.tiles_per_block, plan.fc_blocks, plan.blocks) == \
+            (UPDATE_PLAIN, wpt, tpb, nfc, nfc + 84), B
+    eng.close()
+
+    eng = _bare_engine(2051, 64)
+    assert eng.fc_part is not None
+    plan = _stamped_update(eng, 2051, 64)
+    assert (plan.form, plan.slices, plan.fc_blocks, plan.blocks) == (UPDATE_SPLIT_K, 2, 176, 260)
+    assert int(eng.fc_counters().abs().sum().item()) == 0
+    eng.close()
+
+    eng = _bare_engine(8, 8, loopback_world=2)
+    plan = _stamped_update(eng, 8, 8)
+    assert (plan.form, plan.world_bound, plan.loopback, plan.fc_blocks, plan.blocks) == (UPDATE_EXCHANGE, 2, 1, 88, 172)
+    assert eng.comm_errors() == 0
+    g = torch.zeros(21840, device=eng.device)
+    with pytest.raises(RuntimeError, match="lenet_update: the fused exchange reduces the slabs itself"):
+        torch.ops.csed.lenet_update(*eng.update_args("step")._replace(grad_in=g))
+    # the native executor resolves the plan when it takes the argument block, not at run()
+    with pytest.raises(RuntimeError, match="lenet_update: the exchange timeout must be positive"):
+        torch.classes.csed.LenetStepper().set_update(*eng.update_args("step")._replace(exch_timeout_s=0.0))
     eng.close()
 
 

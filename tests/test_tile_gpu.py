@@ -171,7 +171,7 @@ def test_tile_epoch_tail_on_the_tile_kernel():
     assert _rel(finals[0], finals[1]) < 3e-2
 
 
-# split-K fc gradients (lenet_fused.hip fc_split_slices): per-rank batches > 1024 form each fc
+# split-K fc gradients (lenet_plan.h lenet_update_plan): per-rank batches > 1024 form each fc
 # tile as up to 8 batch slices on all CUs, the tile's last-arriving slice finishing it; against the
 # single-launch FC role only the summation order of the fc sums differs (the conv role is the same)
 @pytest.mark.parametrize("B,dt", [(4096, torch.float16), (2048, torch.bfloat16), (2048, torch.float32)])
@@ -211,7 +211,7 @@ def test_split_k_sgd_steps_and_step_counter():
         torch.cuda.synchronize()
         out.append((eng.flat.data.cpu().clone(), eng.momentum_buf.cpu().clone(), int(eng.step_count.item())))
         if split:  # every tile's arrival counter back at zero
-            assert int(eng.fc_part[8 * 88 * 256:8 * 88 * 256 + 88].view(torch.int32).abs().sum().item()) == 0
+            assert eng.fc_counters().numel() == 88 and int(eng.fc_counters().abs().sum().item()) == 0
     (p1, m1, s1), (p2, m2, s2) = out
     assert s1 == s2 == 3
     assert _rel(p1, p2) < 1e-5 and _rel(m1, m2) < 1e-3

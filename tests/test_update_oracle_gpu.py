@@ -92,8 +92,8 @@ def _assert_within(got: torch.Tensor, want: torch.Tensor, bound: torch.Tensor, w
 
 
 def _fc_counters_zero(eng) -> bool:
-    cnt = eng.fc_part[8 * 88 * 256:8 * 88 * 256 + 88].view(torch.int32)
-    return not bool(cnt.any().item())
+    cnt = eng.fc_counters()  # (the layout's fc_counters_off / fc_tiles: pinned by tests/test_launch_args_cpu.py)
+    return cnt.numel() == 88 and not bool(cnt.any().item())
 
 
 def _reduce(eng, B, grid, out, grad_post, fc_split=None, exchange=False, with_loss=True):
@@ -151,6 +151,8 @@ def test_reduce_integer_inputs_exact(dtype, shape):
 # ------------------------------------------------------------------ (b) reduce mode, real values
 SHAPES_REAL = [(1024, 8, 8), (1024, 33, 33), (1024, 64, 64), (1024, 100, 7), (1024, 200, 200), (1024, 500, 256),
                (1024, 777, 256), (2051, 2051, 256)]
+# the FC configuration each of these batches stands for: (waves per tile, split-K slices) of the launch's plan
+FC_CONFIG = {8: (1, 1), 33: (1, 1), 64: (1, 1), 100: (1, 1), 200: (2, 1), 500: (4, 1), 777: (8, 1), 2051: (8, 2)}
 
 
 @pytest.mark.parametrize("shape", SHAPES_REAL, ids=lambda s: f"B{s[1]}-grid{s[2]}")
@@ -170,6 +172,8 @@ def test_reduce_real_inputs_within_fp32_summation_bound(dtype, shape):
     (n + 2) u S |grad_post|, the slack covering the second-order terms ((n + 1) u < 2.5e-4 here)."""
     eng_b, B, grid = shape
     eng = _engine(dtype, eng_b)
+    plan = eng.update_plan(eng.update_args("reduce", B=B, grid=grid, grad=eng.flat.data, exchange=False))  # (grad: any tensor)
+    assert (plan.waves_per_tile, plan.slices) == FC_CONFIG[B] and not plan.error
     gp = 1.0 / B
     inp = orc.make_inputs(B, grid, dtype, "real", 31 * B + grid)
     ref = orc.reference(inp, B, grid, gp)

@@ -13,7 +13,8 @@ drained, the dispatch retired) falls inside gap_ut.
 
 At per-rank batches that take the sample-tile kernel (csrc/kernels/lenet_tile.hip, B >=
 tile_min_batch()) "train" is lenet_tile's span (its realtime stamps 12 / 13) and the update grid
-is fc_blocks(B) + 84 blocks (the FC blocks first): e.g. --batch 1024 8192 --worlds 1."""
+is the update plan's (FusedLeNetTrainer.update_plan: the FC blocks first, then the CONV blocks): e.g.
+--batch 1024 8192 --worlds 1."""
 import argparse
 import os
 import statistics
@@ -86,17 +87,9 @@ def main():
             du = torch.zeros(n, 8 * 1024, dtype=torch.long, device=dev)
             tile = eng.uses_tile_kernel()
             i_in, i_out = (12, 13) if tile else (22, 23)
-            # fc_blocks(B) (lenet_fused.hip): 88 FC tiles, 8 / waves-per-tile of them per block
-            wpt = 1 if B <= 128 else 2 if B <= 256 else 4 if B <= 512 else 8
-            nfc = 88 if (N > 1 or wpt == 1) else 88 // (8 // wpt)
-            # split-K fc gradients (B > 1024, no exchange): 88 x S FC blocks, S = B / 1024 as a
-            # power of two <= 8 (lenet_fused.hip fc_split_slices; CSED_FC_SLICES forces it)
-            if N == 1 and B > 1024 and eng.fc_part is not None:
-                forced = int(os.environ.get("CSED_FC_SLICES", "0") or 0)
-                S = 1
-                while S * 2 <= 8 and (S * 2 <= forced if forced > 0 else S * 2 * 1024 <= B):
-                    S *= 2
-                nfc = 88 * S
+            # the stamped update's FC and CONV blocks: the launcher's own plan (csrc/kernels/lenet_plan.h)
+            plan = eng.update_plan(eng.update_args("step", fc_split=True))
+            nfc, ncv = plan.fc_blocks, plan.blocks - plan.fc_blocks
             g = stamped_graph(eng, n, dt, du)
             for _ in range(3):
                 dt.zero_()
@@ -112,8 +105,8 @@ def main():
                 u0 = u[:, 0][u[:, 0] > 0].min().item()
                 s3 = u[:, 3].max().item()
                 s4 = u[:, 4][u[:, 4] > 0].max().item()
-                # blocks [0, nfc): the FC role, then the 84 CONV blocks
-                fc_r, cv_r = slice(0, nfc), slice(nfc, nfc + 84)
+                # blocks [0, nfc): the FC role, then the CONV blocks
+                fc_r, cv_r = slice(0, nfc), slice(nfc, nfc + ncv)
                 fc4 = u[fc_r, 4][u[fc_r, 4] > 0].max().item()
                 cv4 = u[cv_r, 4][u[cv_r, 4] > 0].max().item()
                 nt0 = T[i + 1, :, i_in].min().item()

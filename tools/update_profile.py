@@ -75,18 +75,18 @@ def main():
         upd_full(dbg)
         torch.cuda.synchronize()
     st = dbg.view(256, 8).cpu().double()
-    stamps(st, B, "after train")
+    plan = eng.update_plan(eng.update_args("step", cursor=None, dbg=dbg, **alone))
+    stamps(st, plan, "after train")
     for _ in range(3):  # the update again, with nothing in between (its inputs unchanged)
         dbg.zero_()
         upd_full(dbg)
         torch.cuda.synchronize()
-    stamps(dbg.view(256, 8).cpu().double(), B, "after update")
+    stamps(dbg.view(256, 8).cpu().double(), plan, "after update")
 
 
-def stamps(st, B, what):
-    wpt = 1 if B <= 128 else (2 if B <= 256 else (4 if B <= 512 else 8))  # fc_waves_per_tile
-    nfc = 88 if wpt == 1 else 88 // (8 // wpt)  # blocks [0, nfc) FC role, then 84 CONV role blocks
-    nb = nfc + 84
+def stamps(st, plan, what):
+    # blocks [0, nfc) FC role, then the CONV role blocks (the launch's plan, csrc/kernels/lenet_plan.h)
+    wpt, nfc, nb = plan.waves_per_tile, plan.fc_blocks, plan.blocks
     t0 = st[:nb, 0].min()
     rel = (st - t0) * 0.01  # us
     for role, sl, ks in [("CONV", slice(nfc, nb), [0, 1, 2, 3, 4]), ("FC", slice(0, nfc), [0, 1, 2, 3, 4])]:
