@@ -56,6 +56,11 @@ def _common_flags(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("--lr-step-size", type=int, default=None,
                     help="warmup-step: steps between decays (default: one epoch)")
     ap.add_argument("--lr-gamma", type=float, default=0.1, help="warmup-step: decay factor")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
+                    help="keep an exponential moving average of the weights, e += (1 - D) (p - e) after every "
+                         "optimizer step (on the device, inside the update kernel): one more line with its loss "
+                         "and accuracy after each validation line, and results/ema.pth next to results/model.pth "
+                         "(default: off)")
 
 
 def _make_schedule(args, steps_per_epoch: int):
@@ -69,6 +74,40 @@ def _make_schedule(args, steps_per_epoch: int):
     if args.lr_schedule == "warmup-step":
         return LRSchedule.warmup_step(args.lr, warm, args.lr_step_size or steps_per_epoch, args.lr_gamma, total)
     return None
+
+
+def _check_ema_flag(args) -> None:
+    if args.ema_decay is not None and not 0.0 <= args.ema_decay < 1.0:
+        raise SystemExit(f"--ema-decay {args.ema_decay}: expected 0 <= D < 1")
+
+
+def _modular_ema(args, tr, net) -> None:
+    """--ema-decay on the per-op engine: its optimizer averages on the CPU only (optim.FusedSGD.set_ema)."""
+    if tr.opt.on_gpu:
+        raise SystemExit("--ema-decay on a GPU needs --engine fused: the per-op engine's SGD kernel keeps no "
+                         "moving average")
+    tr.opt.set_param_names(n for n, _ in net.named_parameters())
+    tr.opt.set_ema(args.ema_decay)
+
+
+def ema_line(decay: float, avg_loss: float, correct: int, total: int) -> str:
+    """The averaged weights' validation line (a format of its own: the reference has no such line)."""
+    return "EMA weights (decay {:g}): Avg. loss: {:.4f}, Accuracy: {}/{} ({:.2f}%)".format(
+        decay, avg_loss, correct, total, 100.0 * correct / total)
+
+
+@torch.no_grad()
+def _evaluate_ema(tr, net, loader) -> tuple[float, int]:
+    """(summed NLL, correct) of the modular engine's averaged weights: the parameters are swapped for the
+    average for one evaluation pass (the per-op path reads the module's own tensors) and put back."""
+    flat, ema = tr.flat.data, tr.opt.ema_flat
+    keep = flat.clone()
+    flat.copy_(ema)
+    try:
+        total, correct, _ = tr.evaluate(loader)
+        return total.item(), int(correct.item())
+    finally:
+        flat.copy_(keep)
 
 
 def _restore_schedule(sched, path: str) -> None:
@@ -100,6 +139,7 @@ def single_main(argv=None) -> int:
     ap.add_argument("--resume", action="store_true", help="load results/model.pth + optimizer.pth first")
     _common_flags(ap)
     args = ap.parse_args(argv)
+    _check_ema_flag(args)
 
     torch.backends.cudnn.enabled = False  # ref src/train.py:20 (our kernels never use MIOpen)
     torch.manual_seed(args.seed)
@@ -125,6 +165,7 @@ def single_main(argv=None) -> int:
     use_fused = dev.type == "cuda" and args.engine == "fused"
     results = os.path.join(out, "results")
     sched_path = os.path.join(results, "lr_schedule.pth")
+    ema_path = os.path.join(results, "ema.pth")
     sched = _make_schedule(args, (n_train + args.batch_size - 1) // args.batch_size)
     if args.resume:
         _restore_schedule(sched, sched_path)
@@ -141,18 +182,28 @@ def single_main(argv=None) -> int:
             eng.load_optimizer_state_dict(torch.load(os.path.join(results, "optimizer.pth"), weights_only=True))
         if sched is not None:
             eng.set_lr_schedule(sched)
+        if args.ema_decay is not None:
+            eng.set_ema(args.ema_decay)  # (starts at the current weights; --resume: at the saved average)
+            saved = checkpoint.load_ema(ema_path) if args.resume else None
+            if saved is not None:
+                eng.load_ema_state_dict(saved)
 
         def test():
             lsum, correct = eng.evaluate(test_set)
             avg = lsum / len(test_set)
             hist.test_losses.append(avg)
             print(metrics.test_line(avg, correct, len(test_set), time.time() - t0))
+            if args.ema_decay is not None:
+                lsum, correct = eng.evaluate(test_set, ema=True)
+                print(ema_line(args.ema_decay, lsum / len(test_set), correct, len(test_set)))
 
         def save():
             checkpoint.save_model(net, os.path.join(results, "model.pth"))
             checkpoint._atomic_save(opt_state(), os.path.join(results, "optimizer.pth"))
             if sched is not None:
                 checkpoint._atomic_save(sched.state_dict(), sched_path)
+            if args.ema_decay is not None:
+                checkpoint.save_ema(eng.ema_state_dict(), ema_path)
 
         nb = (n_train + args.batch_size - 1) // args.batch_size
         test()
@@ -205,6 +256,11 @@ def single_main(argv=None) -> int:
                                        os.path.join(results, "optimizer.pth"))
         if sched is not None:
             tr.opt.set_lr_schedule(sched)
+        if args.ema_decay is not None:
+            _modular_ema(args, tr, net)
+            saved = checkpoint.load_ema(ema_path) if args.resume else None
+            if saved is not None:
+                tr.opt.load_ema_state_dict(saved)
         train_loader = DeviceLoader(train, args.batch_size, shuffle=True, device=dev,
                                     dtype=ops.compute_dtype() if dev.type == "cuda" else torch.float32)
         tr.bind_loader(train_loader)
@@ -214,6 +270,9 @@ def single_main(argv=None) -> int:
             avg = total.item() / len(test_set)
             hist.test_losses.append(avg)
             print(metrics.test_line(avg, int(correct.item()), len(test_set), time.time() - t0))
+            if args.ema_decay is not None:
+                lsum, ok = _evaluate_ema(tr, net, test_loader)
+                print(ema_line(args.ema_decay, lsum / len(test_set), ok, len(test_set)))
 
         test()
         for epoch in range(1, args.epochs + 1):
@@ -230,6 +289,8 @@ def single_main(argv=None) -> int:
                                                os.path.join(results, "optimizer.pth"))
                     if sched is not None:
                         checkpoint._atomic_save(sched.state_dict(), sched_path)
+                    if args.ema_decay is not None:
+                        checkpoint.save_ema(tr.opt.ema_state_dict(), ema_path)
             test()
 
     if not args.no_plot:
@@ -284,6 +345,7 @@ def dist_main(argv=None) -> int:
                     help="reproduce the reference's metric quirks (loss/bs sums, mean-of-batch-means val)")
     _common_flags(ap)
     args = ap.parse_args(argv)
+    _check_ema_flag(args)
 
     torch.backends.cudnn.enabled = False
     torch.manual_seed(args.seed)
@@ -326,6 +388,9 @@ def dist_main(argv=None) -> int:
         sched = _make_schedule(args, -(-len(sampler) // per_rank))
         if sched is not None:  # (every rank the same table and position: the replicas stay bitwise identical)
             eng.set_lr_schedule(sched)
+        if args.ema_decay is not None:  # (after the constructor's parameter broadcast: the same start everywhere)
+            eng.set_ema(args.ema_decay)
+        ema_sd = eng.ema_state_dict if args.ema_decay is not None else None
         sampler.set_epoch(0)
         order = sampler.indices()
         i = 0
@@ -394,6 +459,9 @@ def dist_main(argv=None) -> int:
             hist.test_losses.append(val_loss)
             acc = 100.0 * correct / n_test
             print(metrics.dist_epoch_line(i, train_loss, val_loss, acc, time.time() - t0), flush=True)
+            if args.ema_decay is not None:
+                lsum, ok = eng.evaluate(test_set, ema=True)
+                print(ema_line(args.ema_decay, lsum / n_test, ok, n_test), flush=True)
             _check_replicas(args, ctx, net, i)
             i += 1
         eng.close()
@@ -407,6 +475,9 @@ def dist_main(argv=None) -> int:
         sched = _make_schedule(args, len(loader))
         if sched is not None:
             tr.opt.set_lr_schedule(sched)
+        if args.ema_decay is not None:
+            _modular_ema(args, tr, net)
+        ema_sd = tr.opt.ema_state_dict if args.ema_decay is not None else None
         tr.bind_loader(loader)
         for i in range(args.epochs):
             sampler.set_epoch(i)
@@ -431,6 +502,9 @@ def dist_main(argv=None) -> int:
             hist.test_losses.append(val_loss)
             acc = 100.0 * correct.item() / n_test
             print(metrics.dist_epoch_line(i, train_loss, val_loss, acc, time.time() - t0), flush=True)
+            if args.ema_decay is not None:
+                lsum, ok = _evaluate_ema(tr, net, test_loader)
+                print(ema_line(args.ema_decay, lsum / n_test, ok, n_test), flush=True)
             _check_replicas(args, ctx, net, i)
 
     barrier(ctx)
@@ -439,5 +513,7 @@ def dist_main(argv=None) -> int:
             plot.plot_loss_curve(hist.train_counter, hist.train_losses, hist.test_counter, hist.test_losses,
                                  os.path.join(args.out_dir, "images/train_test_curve_dist.png"))
         checkpoint.save_model(net, os.path.join(args.out_dir, "model.pt"))  # ref train_dist.py:163-164
+        if ema_sd is not None:  # (model.pt stays the raw weights; the averaged ones go next to it)
+            checkpoint.save_ema(ema_sd(), os.path.join(args.out_dir, "ema.pt"))
     destroy()
     return 0

@@ -169,8 +169,9 @@ TRAIN_FIELDS = ("images", "labels", "perm", "cursor", "B", "rank", "wimg", "para
 UPDATE_FIELDS = ("slab", "grid", "vslab", "B", "grad_in", "grad_out", "params", "momentum", "wimg", "lr", "mom",
                  "dampening", "weight_decay", "nesterov", "step", "ticket", "cursor", "rng_offset", "apply_sgd",
                  "loss_parts", "nparts", "loss_acc", "mfma_dtype", "dbg", "exch_id", "exch_timeout_s", "grad_post",
-                 "fc_part", "lr_table", "lr_pos")
-TrainArgs, UpdateArgs = namedtuple("TrainArgs", TRAIN_FIELDS), namedtuple("UpdateArgs", UPDATE_FIELDS)
+                 "fc_part", "lr_table", "lr_pos", "ema", "ema_decay")
+TrainArgs = namedtuple("TrainArgs", TRAIN_FIELDS)
+UpdateArgs = namedtuple("UpdateArgs", UPDATE_FIELDS, defaults=(None, 0.0))  # (the moving average: off)
 _ENGINE = object()  # (default of a builder's ``cursor``: the engine's own device cursor)
 
 
@@ -273,6 +274,9 @@ class FusedLeNetTrainer:
         self._cap_stream: torch.cuda.Stream | None = None
         self._stepper: tuple | None = None  # (key, csed.LenetStepper), see stepper()
         self.lr_schedule = None  # optim.LRSchedule on the device (set_lr_schedule), or None: constant self.lr
+        self.ema: torch.Tensor | None = None  # the parameters' moving average (set_ema), or None: off
+        self.ema_decay = 0.0
+        self._ema_wimg: torch.Tensor | None = None  # its weight image, packed for evaluate(ema=True)
         self.native_max = native_max_steps()
         # which training kernel a step asks for: 0 auto (the sample-tile kernel, csrc/kernels/lenet_tile.hip,
         # for large 16-bit per-rank batches), 1 the per-sample lenet_train, 2 the sample-tile kernel
@@ -522,7 +526,8 @@ class FusedLeNetTrainer:
         SGD, in one kernel), "reduce" (reduce only, into ``grad``; advances neither cursor nor Philox offset)
         or "apply" (SGD from the already reduced ``grad``).  The launch that applies SGD ("step" / "apply") gets
         the learning-rate schedule's table and position where one is set (set_lr_schedule): it trains at
-        its own step's entry and advances the position.  The kernel that reduces also sums the loss
+        its own step's entry and advances the position.  It also gets the moving average's buffer and decay
+        (set_ema): the lane that writes a parameter updates its average.  The kernel that reduces also sums the loss
         partials (``with_loss``), applies the 16-bit steps' ``grad_scale`` (train_args), runs the fused
         exchange (``exchange``; default: where the engine has one) and, by default exactly without it, gets
         the split-K fc scratch of per-rank batches > 1024 (``fc_split``)."""
@@ -547,7 +552,8 @@ class FusedLeNetTrainer:
             loss_acc=self.loss_acc if loss else None, mfma_dtype=self.mfma, dbg=dbg,
             exch_id=-1 if exch is None else exch.id, exch_timeout_s=2.0 if exch is None else self.exch_timeout_s,
             grad_post=grad_scale if reduces and not in_kernel else 1.0, fc_part=self.fc_part if fc_split else None,
-            lr_table=None if sch is None else sch.table, lr_pos=None if sch is None else sch.pos)
+            lr_table=None if sch is None else sch.table, lr_pos=None if sch is None else sch.pos,
+            ema=self.ema if advances else None, ema_decay=self.ema_decay if advances and self.ema is not None else 0.0)
 
     def update_plan(self, args: UpdateArgs) -> LenetUpdatePlan:
         """The plan of the ``csed::lenet_update`` launch that ``args`` (update_args) describes."""
@@ -649,7 +655,8 @@ class FusedLeNetTrainer:
         """Device tensors a training step advances."""
         return ([self.flat.data, self.momentum_buf, self.wimg, self.step_count, self.cursor, self.rng_offset,
                  self.loss_acc] + ([self.xstage, self.lstage] if self.xstage is not None else [])
-                + ([self.lr_schedule.pos] if self.lr_schedule is not None else []))
+                + ([self.lr_schedule.pos] if self.lr_schedule is not None else [])
+                + ([self.ema] if self.ema is not None else []))
 
     def _stamp(self, key: str, dt: float) -> None:
         self.bringup_s[key] = self.bringup_s.get(key, 0.0) + dt
@@ -771,14 +778,28 @@ class FusedLeNetTrainer:
             self._eval_cache = {id(data): hit}
         return hit[1], hit[2]
 
+    def _eval_weights(self, ema: bool) -> tuple[torch.Tensor, torch.Tensor]:
+        """(weight image, fp32 parameters) an evaluation reads: the engine's own, or (``ema``) the moving
+        average and its image, packed here from the average's current values (csed::lenet_pack)."""
+        if not ema:
+            return self.wimg, self.flat.data
+        if self.ema is None:
+            raise RuntimeError("no moving average is kept (set_ema)")
+        if self._ema_wimg is None:  # (zero-initialised like wimg: the images' padding stays zero)
+            self._ema_wimg = _native.zeros(lenet_layout().wimg_elems, torch.int16, self.device)
+        torch.ops.csed.lenet_pack(self.ema, self._ema_wimg, self.mfma)
+        return self._ema_wimg, self.ema
+
     @torch.no_grad()
-    def evaluate(self, test: MNISTData, order: torch.Tensor | None = None) -> tuple[float, int]:
-        """Forward-only pass over ``test``: (summed NLL, correct).  No dropout."""
+    def evaluate(self, test: MNISTData, order: torch.Tensor | None = None, ema: bool = False) -> tuple[float, int]:
+        """Forward-only pass over ``test``: (summed NLL, correct).  No dropout.  ``ema``: of the averaged
+        parameters (set_ema) instead of the current ones."""
         test, ar = self._device_data(test)
         n = len(test)
         order = ar if order is None else order.to(self.device)
         nparts = min(n, 256)
-        torch.ops.csed.lenet_eval(test.images, test.labels, order, n, self.wimg, self.flat.data, MNIST_MEAN,
+        wimg, params = self._eval_weights(ema)
+        torch.ops.csed.lenet_eval(test.images, test.labels, order, n, wimg, params, MNIST_MEAN,
                                   MNIST_STD, self.eval_parts, None, self.mfma)
         # (the 256 partial pairs summed on the host, in fixed order: a device reduction would be a
         # torch kernel whose code object loads at its first launch -- inside epoch 0)
@@ -786,12 +807,13 @@ class FusedLeNetTrainer:
         return parts[0], int(round(parts[1]))
 
     @torch.no_grad()
-    def eval_logp(self, test: MNISTData) -> torch.Tensor:
+    def eval_logp(self, test: MNISTData, ema: bool = False) -> torch.Tensor:
         test, ar = self._device_data(test)
         n = len(test)
         out = torch.empty(n, 10, device=self.device)
-        torch.ops.csed.lenet_eval(test.images, test.labels, ar, n, self.wimg,
-                                  self.flat.data, MNIST_MEAN, MNIST_STD, self.eval_parts, out, self.mfma)
+        wimg, params = self._eval_weights(ema)
+        torch.ops.csed.lenet_eval(test.images, test.labels, ar, n, wimg, params, MNIST_MEAN, MNIST_STD,
+                                  self.eval_parts, out, self.mfma)
         return out
 
     # ------------------------------------------------------------ optimizer io
@@ -829,6 +851,38 @@ class FusedLeNetTrainer:
         blocks hold the old rate or table: dropped, as in load_optimizer_state_dict."""
         self.lr_schedule = None if schedule is None else schedule.to(self.device)
         self.invalidate()
+
+    def set_ema(self, decay: float | None) -> None:
+        """Keep an exponential moving average of the parameters, ``e <- e + (1 - decay) * (p_new - e)`` in
+        fp32, updated on the device by every launch that applies SGD (full and tail steps, at any world
+        size: the summed gradient is the same on every rank, so are the averages), started at a copy of
+        the current parameters.  None switches it off and frees the buffer.  Captured graphs and the
+        executor's argument blocks hold the old buffer or none: dropped, as in set_lr_schedule."""
+        if decay is None:
+            self.ema, self.ema_decay, self._ema_wimg = None, 0.0, None
+        else:
+            if not 0.0 <= float(decay) < 1.0:
+                raise ValueError(f"ema decay {decay}: expected 0 <= decay < 1")
+            if self.ema is None:  # (the extension's own fill; the copy below is a device-to-device memcpy)
+                self.ema = _native.zeros(self.flat.data.shape, torch.float32, self.device)
+            self.ema.copy_(self.flat.data)
+            self.ema_decay = float(decay)
+        self.invalidate()
+
+    def ema_state_dict(self) -> dict:
+        """The averaged parameters under ``Net``'s parameter names (fp32 CPU tensors): loads into the
+        reference ``Net`` with ``load_state_dict``."""
+        if self.ema is None:
+            raise RuntimeError("no moving average is kept (set_ema)")
+        return {n: self.flat.view(self.ema, i).detach().cpu().clone()
+                for i, (n, _) in enumerate(self.model.named_parameters())}
+
+    def load_ema_state_dict(self, sd: dict) -> None:
+        """Restore ``ema_state_dict()``'s values (EMA must be on: the decay is not part of the file)."""
+        if self.ema is None:
+            raise RuntimeError("no moving average is kept (set_ema)")
+        for i, (n, _) in enumerate(self.model.named_parameters()):
+            self.flat.view(self.ema, i).copy_(sd[n])
 
     def params_changed(self) -> None:
         """Call after writing the model parameters from outside (e.g. a checkpoint load)."""

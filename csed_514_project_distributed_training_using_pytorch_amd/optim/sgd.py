@@ -37,7 +37,25 @@ class FusedSGD(torch.optim.SGD):
         self.step_count = torch.zeros(1, dtype=torch.long, device=dev)
         self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self.grad_scale = 1.0
+        self.param_names: list[str] | None = None  # (set_param_names: the keys of ema_state_dict)
         self.lr_schedule: LRSchedule | None = None
+        self.ema_flat: torch.Tensor | None = None  # the parameters' moving average (set_ema), or None: off
+        self.ema_decay = 0.0
+
+    def set_ema(self, decay: float | None) -> None:
+        """Keep an exponential moving average of the parameters, ``e <- e + (1 - decay) * (p - e)`` in fp32
+        after every step, started at a copy of the current parameters (``ema_flat``); None switches it off
+        and frees the buffer.  CPU parameters only: csed::sgd_flat has no average yet (the fused engine's
+        update kernel has), and a GPU optimizer raises instead of averaging with torch kernels."""
+        if decay is None:
+            self.ema_flat, self.ema_decay = None, 0.0
+            return
+        if self.on_gpu:
+            raise NotImplementedError("FusedSGD keeps a moving average on CPU parameters only: csed::sgd_flat "
+                                      "does not update one (use the fused engine's set_ema on a GPU)")
+        if not 0.0 <= float(decay) < 1.0:
+            raise ValueError(f"ema decay {decay}: expected 0 <= decay < 1")
+        self.ema_flat, self.ema_decay = self.flat.data.detach().clone(), float(decay)
 
     def set_lr_schedule(self, schedule: LRSchedule | None) -> None:
         """Train at ``schedule``'s rates from its current position (moved to the parameters' device) instead
@@ -45,6 +63,13 @@ class FusedSGD(torch.optim.SGD):
         reads the table entry of its step and advances the position itself, so a captured step serves
         the whole schedule."""
         self.lr_schedule = None if schedule is None else schedule.to(self.flat.device)
+
+    def set_param_names(self, names) -> None:
+        """The parameters' names in the optimizer's order (``[n for n, _ in model.named_parameters()]``)."""
+        names = list(names)
+        if len(names) != len(self.flat.params):
+            raise ValueError("one name per parameter")
+        self.param_names = names
 
     @property
     def on_gpu(self) -> bool:
@@ -88,6 +113,9 @@ class FusedSGD(torch.optim.SGD):
                 buf.mul_(m).add_(d, alpha=1 - damp)
             d = d + m * buf if nest else buf
         p.add_(d, alpha=-lr)
+        if self.ema_flat is not None:  # (1 - decay formed in fp32 from the fp32 decay, as the kernels form it)
+            w = (torch.ones((), dtype=torch.float32) - torch.tensor(self.ema_decay, dtype=torch.float32)).item()
+            self.ema_flat.add_(p - self.ema_flat, alpha=w)
         self.step_count += 1
 
     # ---- torch.optim.SGD-compatible state dict -------------------------------------------------
@@ -99,6 +127,23 @@ class FusedSGD(torch.optim.SGD):
         if self.lr_schedule is not None:  # (what a torch scheduler leaves in the param group)
             sd["param_groups"][0]["lr"] = self.lr_schedule.current_lr()
         return sd
+
+    def ema_state_dict(self) -> dict:
+        """The averaged parameters under the model's parameter names where the optimizer was given them
+        (``set_param_names``; else their indices): loads into the same module with ``load_state_dict``."""
+        if self.ema_flat is None:
+            raise RuntimeError("no moving average is kept (set_ema)")
+        names = self.param_names or [str(i) for i in range(len(self.flat.params))]
+        return {n: self.flat.view(self.ema_flat, i).detach().cpu().clone() for i, n in enumerate(names)}
+
+    def load_ema_state_dict(self, sd: dict) -> None:
+        """Restore ``ema_state_dict()``'s values (EMA must be on: the decay is not part of the file)."""
+        if self.ema_flat is None:
+            raise RuntimeError("no moving average is kept (set_ema)")
+        names = self.param_names or [str(i) for i in range(len(self.flat.params))]
+        with torch.no_grad():
+            for i, n in enumerate(names):
+                self.flat.view(self.ema_flat, i).copy_(sd[n])
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)

@@ -3,6 +3,8 @@
 * ``results/model.pth`` / ``model.pt``: ``Net.state_dict()`` -- the 8 fp32 CPU
   tensors ``conv1.weight ... fc2.bias`` (no ``module.`` prefix).
 * ``results/optimizer.pth``: ``torch.optim.SGD.state_dict()`` layout.
+* ``results/ema.pth`` / ``ema.pt`` (``--ema-decay`` only; no counterpart in the reference): the
+  parameters' exponential moving average under the same 8 names, so it loads into ``Net`` too.
 
 Tensors are cloned to standalone CPU storages before ``torch.save`` (our
 parameters are views into one flat device buffer), so the files are ordinary
@@ -66,3 +68,15 @@ def load_checkpoint(model, opt=None, model_path="results/model.pth", opt_path="r
             own[k].copy_(v)  # copy into existing (possibly flat-buffer) storage
     if opt is not None and opt_path and Path(opt_path).exists():
         opt.load_state_dict(torch.load(opt_path, map_location=map_location, weights_only=True))
+
+
+def save_ema(ema_state: dict, path="results/ema.pth") -> None:
+    """The averaged parameters (an engine's / optimizer's ``ema_state_dict()``) as a model checkpoint."""
+    _atomic_save(_cpu_clone(ema_state), path)
+
+
+def load_ema(path="results/ema.pth", map_location="cpu") -> dict | None:
+    """``save_ema``'s dict for ``load_ema_state_dict``, or None where the run kept no average."""
+    if not Path(path).exists():
+        return None
+    return torch.load(path, map_location=map_location, weights_only=True)

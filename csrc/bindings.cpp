@@ -98,6 +98,19 @@ void check_lr_schedule(const char* op, const Tensor& on, const optional<Tensor>&
   TORCH_CHECK(lr_table->numel() >= 1 && lr_table->numel() <= INT32_MAX, op, ": lr_table needs at least one entry");
 }
 
+// The parameters' exponential moving average (optional): one fp32 value per parameter on their device,
+// updated by the launch that applies SGD with a decay in [0, 1).
+void check_ema(const char* op, const Tensor& params, const optional<Tensor>& ema, double ema_decay, bool apply_sgd) {
+  if (!ema.has_value()) return;
+  TORCH_CHECK(apply_sgd, op, ": ema comes only with apply_sgd (a reduce-only launch changes no parameter)");
+  TORCH_CHECK(ema->is_cuda() && ema->device() == params.device(), op, ": ema must be on the parameters' device");
+  TORCH_CHECK(ema->scalar_type() == at::kFloat && ema->is_contiguous(), op, ": ema must be contiguous float32");
+  TORCH_CHECK(ema->numel() == params.numel(), op, ": ema must hold one value per parameter (", params.numel(),
+              "), got ", ema->numel());
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(ema->data_ptr()) & 15) == 0, op, ": ema must be 16-byte aligned");
+  TORCH_CHECK(ema_decay >= 0.0 && ema_decay < 1.0, op, ": ema_decay must be in [0, 1), got ", ema_decay);
+}
+
 void sgd_flat(Tensor& p, const Tensor& g, Tensor& buf, double lr, double momentum, double dampening,
               double weight_decay, bool nesterov, double grad_scale, Tensor& step, Tensor& ticket,
               const optional<Tensor>& lr_table, const optional<Tensor>& lr_pos) {
@@ -841,7 +854,8 @@ csed::LenetUpdateArgs update_args(const Tensor& slab, int64_t grid, const Tensor
                                   const optional<Tensor>& loss_parts, const optional<Tensor>& loss_acc,
                                   int64_t mfma_dtype, const optional<Tensor>& dbg, int64_t exch_id,
                                   double exch_timeout_s, double grad_post, const optional<Tensor>& fc_part,
-                                  const optional<Tensor>& lr_table, const optional<Tensor>& lr_pos) {
+                                  const optional<Tensor>& lr_table, const optional<Tensor>& lr_pos,
+                                  const optional<Tensor>& ema, double ema_decay) {
   dev(slab, "slab"); dev(params, "params"); dev(momentum, "momentum"); dev(wimg, "wimg");
   TORCH_CHECK(params.numel() == csed::lenet_param_count() && momentum.numel() == params.numel(),
               "lenet_update: params / momentum must hold the 21840 flat LeNet parameters");
@@ -878,6 +892,11 @@ csed::LenetUpdateArgs update_args(const Tensor& slab, int64_t grid, const Tensor
     a.lr_table = lr_table->data_ptr<float>(); a.lr_len = (int)lr_table->numel();
     a.lr_pos = lr_pos->data_ptr<int64_t>();
   }
+  // the parameters' moving average, updated by the launch that applies SGD
+  check_ema("lenet_update", params, ema, ema_decay, apply_sgd);
+  if (ema.has_value()) {
+    a.ema = ema->data_ptr<float>(); a.ema_decay = (float)ema_decay;
+  }
   return a;
 }
 
@@ -897,12 +916,13 @@ void lenet_update(const Tensor& slab, int64_t grid, const Tensor& vslab, int64_t
                   const optional<Tensor>& rng_offset, bool apply_sgd, const optional<Tensor>& loss_parts,
                   int64_t nparts, const optional<Tensor>& loss_acc, int64_t mfma_dtype, const optional<Tensor>& dbg,
                   int64_t exch_id, double exch_timeout_s, double grad_post, const optional<Tensor>& fc_part,
-                  const optional<Tensor>& lr_table, const optional<Tensor>& lr_pos) {
+                  const optional<Tensor>& lr_table, const optional<Tensor>& lr_pos, const optional<Tensor>& ema,
+                  double ema_decay) {
   const c10::DeviceGuard gd(params.device());
   const csed::LenetUpdateArgs a =
       update_args(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
                   nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts, loss_acc, mfma_dtype, dbg,
-                  exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos);
+                  exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos, ema, ema_decay);
   csed::comm::IpcPeers px;
   update_plan(a, &px);
   CHECK_HIP(csed::launch_lenet_update(a, optpt<float>(loss_parts), (int)nparts, optpt<float>(loss_acc),
@@ -1052,12 +1072,12 @@ struct LenetStepper : torch::CustomClassHolder {
                   optional<Tensor> cursor, optional<Tensor> rng_offset, bool apply_sgd, optional<Tensor> loss_parts_t,
                   int64_t nparts_, optional<Tensor> loss_acc_t, int64_t mfma_dtype, optional<Tensor> dbg,
                   int64_t exch_id, double exch_timeout_s, double grad_post, optional<Tensor> fc_part,
-                  optional<Tensor> lr_table, optional<Tensor> lr_pos) {
+                  optional<Tensor> lr_table, optional<Tensor> lr_pos, optional<Tensor> ema, double ema_decay) {
     TORCH_CHECK(apply_sgd && !grad_in && !grad_out && cursor, "LenetStepper: set_update takes a full step at a cursor");
     const csed::LenetUpdateArgs a =
         update_args(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
                     nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts_t, loss_acc_t, mfma_dtype, dbg,
-                    exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos);
+                    exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos, ema, ema_decay);
     csed::comm::IpcPeers peers;
     update_plan(a, &peers);  // the exchange's view and the plan's error once, here: a bad block never reaches run()
     ua = a;
@@ -1066,7 +1086,7 @@ struct LenetStepper : torch::CustomClassHolder {
     loss_acc = optpt<float>(loss_acc_t);
     nparts = nparts_;
     keep_u = {slab,   vslab,      params,       momentum,   wimg, step,   ticket,
-              cursor, rng_offset, loss_parts_t, loss_acc_t, dbg,  fc_part, lr_table, lr_pos};
+              cursor, rng_offset, loss_parts_t, loss_acc_t, dbg,  fc_part, lr_table, lr_pos, ema};
   }
 
   void run(int64_t k) {
@@ -1128,7 +1148,8 @@ TORCH_LIBRARY(csed, m) {
         "bool nesterov, Tensor(e!) step, Tensor(f!) ticket, Tensor(g!)? cursor, Tensor(h!)? rng_offset, "
         "bool apply_sgd, Tensor? loss_parts, int nparts, Tensor(i!)? loss_acc, int mfma_dtype, "
         "Tensor(j!)? dbg=None, int exch_id=-1, float exch_timeout_s=2.0, float grad_post=1.0, "
-        "Tensor(k!)? fc_part=None, Tensor? lr_table=None, Tensor(l!)? lr_pos=None) -> ()");
+        "Tensor(k!)? fc_part=None, Tensor? lr_table=None, Tensor(l!)? lr_pos=None, Tensor(m!)? ema=None, "
+        "float ema_decay=0.0) -> ()");
   m.def("lenet_eval(Tensor images, Tensor labels, Tensor order, int n, Tensor wimg, Tensor params, float mean, "
         "float std, Tensor(a!) out_parts, Tensor(b!)? logp_out, int mfma_dtype, int kernel=0) -> ()");
   m.def("gather_normalize(Tensor src, Tensor idx, Tensor? cursor, int B, float mean, float std, Tensor(a!) out, "

@@ -1430,10 +1430,12 @@ __global__ void __launch_bounds__(512) lenet_stage_kernel(LenetStageArgs st, con
 // Final consumer of one parameter's gradient: export or SGD step.  p / m are
 // params[i] / momentum[i], loaded by the caller at kernel entry so their
 // round trip overlaps the gradient loads instead of following them.  lr: the launch's learning
-// rate (a.lr, or the caller's entry of the device-resident schedule).
-template <typename T>
+// rate (a.lr, or the caller's entry of the device-resident schedule).  EMA (a.ema set: the launcher's
+// choice of instantiation): e is the parameter's old moving average ema[i], loaded by the caller with
+// p / m; the new one, e + (1 - decay) * (p_new - e), is stored after the parameter.
+template <typename T, bool EMA>
 __device__ __forceinline__ void finish_param(const LenetUpdateArgs& a, int i, float gsum, bool first, float p,
-                                             float m, int d0, int d1, float lr) {
+                                             float m, int d0, int d1, float lr, float e) {
   if (!a.apply_sgd) {
     a.grad_out[i] = gsum;
     return;
@@ -1449,15 +1451,17 @@ __device__ __forceinline__ void finish_param(const LenetUpdateArgs& a, int i, fl
   p = fmaf(-lr, d, p);
   a.params[i] = p;
   write_slots<T>(a.wimg, d0, d1, p);
+  if constexpr (EMA) a.ema[i] = fmaf(1.f - a.ema_decay, p - e, e);
 }
 
 // finish_param for 4 consecutive fc1 weights i .. i+3 (16-byte aligned; their weight-image
 // slots d0 .. d0+3 are consecutive and 8-byte aligned): the same arithmetic per element,
 // one wide store per array instead of four
-template <typename T>
+template <typename T, bool EMA>
 __device__ __forceinline__ void finish_param4(const LenetUpdateArgs& a, int i, float4 gsum, bool first, float4 p4,
-                                              float4 m4, int d0, float lr) {
+                                              float4 m4, int d0, float lr, float4 e4) {
   float gv[4] = {gsum.x, gsum.y, gsum.z, gsum.w}, pv[4] = {p4.x, p4.y, p4.z, p4.w}, mv[4] = {m4.x, m4.y, m4.z, m4.w};
+  float ev[4] = {e4.x, e4.y, e4.z, e4.w};
   if (!a.apply_sgd || a.grad_out) *reinterpret_cast<float4*>(a.grad_out + i) = gsum;
   if (!a.apply_sgd) return;
   u16x4 h;
@@ -1476,6 +1480,12 @@ __device__ __forceinline__ void finish_param4(const LenetUpdateArgs& a, int i, f
   if (a.mom != 0.f) *reinterpret_cast<float4*>(a.momentum + i) = make_float4(mv[0], mv[1], mv[2], mv[3]);
   *reinterpret_cast<float4*>(a.params + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
   if constexpr (!std::is_same<T, float>::value) *reinterpret_cast<u16x4*>(a.wimg + d0) = h;
+  if constexpr (EMA) {
+    const float w = 1.f - a.ema_decay;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ev[j] = fmaf(w, pv[j] - ev[j], ev[j]);
+    *reinterpret_cast<float4*>(a.ema + i) = make_float4(ev[0], ev[1], ev[2], ev[3]);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1731,8 +1741,9 @@ __device__ __forceinline__ void ll_poll(const comm::IpcPeers& px, const XPtrs<R>
 // float[4][UP_C*4] in LDS.  XW: 0 = no exchange, else the fused exchange's world bound
 // (2, 4 or 8 >= px.world).  SCHED: the learning rate comes from the device-resident schedule
 // (a.lr_table / a.lr_pos) -- its own instantiations, so a launch without a table runs the code it
-// ran before the schedule existed: no load, no barrier, no ticket.
-template <typename T, int XW, bool LBC = false, bool SCHED = false>
+// ran before the schedule existed: no load, no barrier, no ticket.  EMA: the launch keeps the parameters'
+// moving average (a.ema set) -- likewise its own instantiations (see launch_lenet_update).
+template <typename T, int XW, bool LBC = false, bool SCHED = false, bool EMA = false>
 __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ vslab, int B, float* loss_parts,
                             int nparts, float* loss_acc, const comm::IpcPeers& px, uint64_t timeout_ticks, int blk,
                             int nblk, int tid, float4* part_, float* part2_, int fc_tpb, int fc_sl_arg) {
@@ -1825,12 +1836,13 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
     // the half's first wave owns slab slots pbc*64 + ht (16 float4 columns) = parameter pi
     // (-1: padding slot): prefetch p / m now
     const int pi = slot_param(pbc * (UP_C * 4) + min(ht, 63));
-    float p0 = 0.f, m0 = 0.f;
+    float p0 = 0.f, m0 = 0.f, e0 = 0.f;
     int d0 = -1, d1 = -1;
     auto pm_loads = [&]() {
       if (a.apply_sgd && ht < 64) {
         p0 = a.params[max(pi, 0)];
         m0 = a.momentum[max(pi, 0)];
+        if constexpr (EMA) e0 = a.ema[max(pi, 0)];  // (the old average rides with p / m)
       }
       image_slots_flat(max(pi, 0), d0, d1);  // (lanes without a parameter store nothing)
     };
@@ -1905,7 +1917,7 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
         ll_poll<1, XR, LBC>(px, xp, tag_now(), pbc * (UP_C * 4) + ht, live, g, timeout_ticks, timed_out,
                        a.dbg && tid == 0 && blk < a.dbg_blocks ? a.dbg + blk * 8 : nullptr, blk);
       }
-      finish_param<T>(a, pi, g[0], first, p0, m0, d0, d1, lr_now());
+      finish_param<T, EMA>(a, pi, g[0], first, p0, m0, d0, d1, lr_now(), e0);
     }
     USTAMP(4);
     if (pb == 0 && loss_parts && tid < 64) {
@@ -1960,6 +1972,7 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
     // column i), their p / m
     int pidx[4];
     float pp[4] = {0.f, 0.f, 0.f, 0.f}, pm[4] = {0.f, 0.f, 0.f, 0.f};
+    float pe[4] = {0.f, 0.f, 0.f, 0.f};  // their old moving averages (EMA)
     // fc1 weight tiles (wave-uniform) finish in row layout: lane = (row, 4 columns), one
     // float4 per array (finish_param4); the others per element in the MFMA layout
     const bool vec = live_tile && fc1 && nt < 20;
@@ -1975,6 +1988,7 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
       if (a.apply_sgd && sub == 0 && fin && !vec) {
         pp[r] = a.params[max(pidx[r], 0)];
         pm[r] = a.momentum[max(pidx[r], 0)];
+        if constexpr (EMA) pe[r] = a.ema[max(pidx[r], 0)];
       }
     }
     if (a.apply_sgd && sub == 0 && fin && vec) {
@@ -1982,6 +1996,10 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
       const float4 m4 = *reinterpret_cast<const float4*>(a.momentum + vidx);
       pp[0] = p4.x; pp[1] = p4.y; pp[2] = p4.z; pp[3] = p4.w;
       pm[0] = m4.x; pm[1] = m4.y; pm[2] = m4.z; pm[3] = m4.w;
+      if constexpr (EMA) {
+        const float4 e4 = *reinterpret_cast<const float4*>(a.ema + vidx);
+        pe[0] = e4.x; pe[1] = e4.y; pe[2] = e4.z; pe[3] = e4.w;
+      }
     }
     // fc destinations in the weight images (no table lookups for fc)
     int fd[4];
@@ -2165,6 +2183,7 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
     // output, four in a row).
     asm volatile("" ::"v"(pp[0]), "v"(pp[1]), "v"(pp[2]), "v"(pp[3]), "v"(pm[0]), "v"(pm[1]), "v"(pm[2]),
                  "v"(pm[3]));
+    if constexpr (EMA) asm volatile("" ::"v"(pe[0]), "v"(pe[1]), "v"(pe[2]), "v"(pe[3]));  // (and the old averages)
     // fixed-order combine of the tile's wpt partials (reuses the CONV role's LDS)
     float* pfc = reinterpret_cast<float*>(part_);
     if (wpt > 1) {  // uniform
@@ -2246,11 +2265,16 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
               const float4 m4 = *reinterpret_cast<const float4*>(a.momentum + vidx);
               pp[0] = p4.x; pp[1] = p4.y; pp[2] = p4.z; pp[3] = p4.w;
               pm[0] = m4.x; pm[1] = m4.y; pm[2] = m4.z; pm[3] = m4.w;
+              if constexpr (EMA) {
+                const float4 e4 = *reinterpret_cast<const float4*>(a.ema + vidx);
+                pe[0] = e4.x; pe[1] = e4.y; pe[2] = e4.z; pe[3] = e4.w;
+              }
             } else {
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
                 pp[r] = a.params[max(pidx[r], 0)];
                 pm[r] = a.momentum[max(pidx[r], 0)];
+                if constexpr (EMA) pe[r] = a.ema[max(pidx[r], 0)];
               }
             }
           }
@@ -2275,12 +2299,13 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
         __builtin_amdgcn_wave_barrier();
         const float4 gv = *reinterpret_cast<const float4*>(tr + (lane >> 2) * 16 + 4 * (lane & 3));
         if (vrow < 50)
-          finish_param4<T>(a, vidx, gv, first, make_float4(pp[0], pp[1], pp[2], pp[3]),
-                           make_float4(pm[0], pm[1], pm[2], pm[3]), I_F1 + vrow * LD_F1 + vcol, lr);
+          finish_param4<T, EMA>(a, vidx, gv, first, make_float4(pp[0], pp[1], pp[2], pp[3]),
+                           make_float4(pm[0], pm[1], pm[2], pm[3]), I_F1 + vrow * LD_F1 + vcol, lr,
+                           make_float4(pe[0], pe[1], pe[2], pe[3]));
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (pidx[r] >= 0) finish_param<T>(a, pidx[r], g[r], first, pp[r], pm[r], fd[r], -1, lr);
+          if (pidx[r] >= 0) finish_param<T, EMA>(a, pidx[r], g[r], first, pp[r], pm[r], fd[r], -1, lr, pe[r]);
       }
       }  // do_fin
       USTAMP(4);
@@ -2323,7 +2348,7 @@ struct UpdateKargs {
   LenetUpdateArgs a; const float* vslab; int B; float* loss_parts; int nparts; float* loss_acc;
   uint64_t timeout_ticks; int fc_tpb; int fc_sl;
 };
-template <typename T, int XW, bool LBC = false, bool SCHED = false>
+template <typename T, int XW, bool LBC = false, bool SCHED = false, bool EMA = false>
 __global__ void __launch_bounds__(UP_NT) lenet_update_kernel(LenetUpdateArgs a, const float* __restrict__ vslab,
                                                              int B, float* loss_parts, int nparts,
                                                              float* loss_acc, uint64_t timeout_ticks, int fc_tpb,
@@ -2331,13 +2356,13 @@ __global__ void __launch_bounds__(UP_NT) lenet_update_kernel(LenetUpdateArgs a, 
   prefetch_kernargs<sizeof(UpdateKargs) + sizeof(comm::IpcPeers)>();  // (+ gridDim.x after px)
   __shared__ float4 part[UP_S][UP_C];
   __shared__ float part2[4][UP_C * 4];
-  update_role<T, XW, LBC, SCHED>(a, vslab, B, loss_parts, nparts, loss_acc, px, timeout_ticks, blockIdx.x, gridDim.x,
+  update_role<T, XW, LBC, SCHED, EMA>(a, vslab, B, loss_parts, nparts, loss_acc, px, timeout_ticks, blockIdx.x, gridDim.x,
                               threadIdx.x, &part[0][0], &part2[0][0], fc_tpb, fc_sl);
 }
 
 // SGD from an already-reduced gradient (DDP: after the all-reduce).  SCHED: at the schedule's
 // learning rate (see update_role; a uniform load here: nothing is in flight that it could delay).
-template <typename T, bool SCHED = false>
+template <typename T, bool SCHED = false, bool EMA = false>
 __global__ void lenet_sgd_kernel(LenetUpdateArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool first = (a.step && a.dampening != 0.f) ? a.step[0] == 0 : false;
@@ -2346,7 +2371,9 @@ __global__ void lenet_sgd_kernel(LenetUpdateArgs a) {
   if (i < NP) {
     int d0, d1;
     image_slots(i, d0, d1);
-    finish_param<T>(a, i, a.grad_in[i], first, a.params[i], a.momentum[i], d0, d1, lr);
+    float e = 0.f;
+    if constexpr (EMA) e = a.ema[i];
+    finish_param<T, EMA>(a, i, a.grad_in[i], first, a.params[i], a.momentum[i], d0, d1, lr, e);
   }
   if (SCHED || a.dampening != 0.f) {
     __syncthreads();
@@ -2427,9 +2454,18 @@ hipError_t launch_lenet_update(const LenetUpdateArgs& a, float* loss_parts, int 
   }
   const LenetUpdatePlan p = lenet_update_plan(a, px);
   if (p.error) return hipErrorInvalidValue;
+  // The moving average is no plan dimension: form, grid and trailing arguments are those of the launch
+  // without one.  The kernels take it as a template flag chosen here from a.ema != nullptr, not as a
+  // run-time test: measured (profiles/ema.md), the run-time test on a.ema cost the EMA-off step 0.58 us
+  // of 13.26, far outside the parent's own spread.  It goes with SGD alone, and its fc1 rows are read and
+  // written as float4 like the parameters'.
+  if (a.ema && (!a.apply_sgd || !(a.ema_decay >= 0.f && a.ema_decay < 1.f) || ((uintptr_t)a.ema & 15)))
+    return hipErrorInvalidValue;
   if (p.form == kUpdateSgd) {
     CSED_DISPATCH_UPDATE(a.mfma_dtype, {
-      void (*kern)(LenetUpdateArgs) = p.sched ? lenet_sgd_kernel<scalar_t, true> : lenet_sgd_kernel<scalar_t, false>;
+      void (*kern)(LenetUpdateArgs) =
+          a.ema ? (p.sched ? lenet_sgd_kernel<scalar_t, true, true> : lenet_sgd_kernel<scalar_t, false, true>)
+                : (p.sched ? lenet_sgd_kernel<scalar_t, true> : lenet_sgd_kernel<scalar_t, false>);
       hipLaunchKernelGGL(kern, dim3(p.blocks), dim3(256), 0, s, a);
     });
     return hipGetLastError();
@@ -2440,7 +2476,9 @@ hipError_t launch_lenet_update(const LenetUpdateArgs& a, float* loss_parts, int 
   void (*kern)(LenetUpdateArgs, const float*, int, float*, int, float*, uint64_t, int, int, comm::IpcPeers) = nullptr;
 #define CSED_UPDATE_PICK(W, L)               \
   if (p.world_bound == W && p.loopback == L) \
-  kern = p.sched ? lenet_update_kernel<scalar_t, W, L, true> : lenet_update_kernel<scalar_t, W, L, false>
+  kern = a.ema ? (p.sched ? lenet_update_kernel<scalar_t, W, L, true, true>                \
+                          : lenet_update_kernel<scalar_t, W, L, false, true>)              \
+               : (p.sched ? lenet_update_kernel<scalar_t, W, L, true> : lenet_update_kernel<scalar_t, W, L, false>)
   if (p.world_bound) {
     CSED_DISPATCH_UPDATE(a.mfma_dtype, {
       CSED_UPDATE_PICK(2, true);

@@ -306,6 +306,11 @@ struct LenetUpdateArgs {
   // entry, and the last block to take a ticket advances lr_pos[0] (once per SGD-applying launch).
   // lr_pos is the schedule's own counter: step[0] only encodes "momentum buffer exists".
   const float* lr_table; int lr_len; int64_t* lr_pos;
+  // Exponential moving average of the parameters (optional; apply_sgd only): the lane in which a
+  // parameter's new value is final also writes ema[i] += (1 - ema_decay) * (p_new - ema[i]), in fp32,
+  // from the old ema[i] it loaded with p and m at kernel entry.  Null: off.  No plan dimension: form and
+  // grid are those of the launch without it; the launcher picks the kernels' EMA instantiation from it.
+  float* ema; float ema_decay;
 };
 int64_t lenet_exch_words();
 int lenet_forced_fc_slices();  // CSED_FC_SLICES (0: automatic), read once per process
