@@ -63,6 +63,62 @@ def _common_flags(ap: argparse.ArgumentParser) -> None:
                          "(default: off)")
 
 
+def _optimizer_flags(ap: argparse.ArgumentParser) -> None:
+    ap.add_argument("--optimizer", choices=["sgd", "adam", "adamw"], default="sgd",
+                    help="sgd (the reference's), or torch.optim.Adam's / AdamW's rule: on a GPU inside the fused "
+                         "engine's update kernel, with --device cpu torch's own optimizer; --momentum is SGD's")
+    ap.add_argument("--beta1", type=float, default=0.9, help="adam / adamw: decay of the first moment")
+    ap.add_argument("--beta2", type=float, default=0.999, help="adam / adamw: decay of the second moment")
+    ap.add_argument("--eps", type=float, default=1e-8, help="adam / adamw: added to the denominator")
+    ap.add_argument("--weight-decay", type=float, default=0.0,
+                    help="L2 penalty added to the gradient (sgd, adam) or decoupled decay (adamw)")
+
+
+def _check_optimizer_flags(args) -> None:
+    for flag, v in (("--beta1", args.beta1), ("--beta2", args.beta2)):
+        if not 0.0 <= v < 1.0:
+            raise SystemExit(f"{flag} {v}: expected 0 <= beta < 1")
+    if not args.eps > 0.0:
+        raise SystemExit(f"--eps {args.eps}: expected a positive value")
+    if args.weight_decay < 0.0:
+        raise SystemExit(f"--weight-decay {args.weight_decay}: expected a value >= 0")
+
+
+def _optimizer_kw(args) -> dict:
+    """What --optimizer and its flags add to a trainer's arguments (nothing but the weight decay for sgd)."""
+    kw = {"weight_decay": args.weight_decay}
+    if args.optimizer != "sgd":
+        kw.update(optimizer=args.optimizer, betas=(args.beta1, args.beta2), eps=args.eps)
+    return kw
+
+
+def _modular_adam(args, tr, net) -> None:
+    """--optimizer adam / adamw on the per-op engine: torch's own optimizer, on the CPU only."""
+    if args.optimizer == "sgd":
+        return
+    if tr.opt.on_gpu:
+        raise SystemExit(f"--optimizer {args.optimizer} on a GPU needs --engine fused: the per-op engine's SGD "
+                         "kernel applies no other rule")
+    if args.lr_schedule != "constant" or args.ema_decay is not None:
+        raise SystemExit(f"--lr-schedule and --ema-decay with --optimizer {args.optimizer} need the fused engine "
+                         "(a GPU): on the CPU the optimizer is torch's own")
+    cls = torch.optim.AdamW if args.optimizer == "adamw" else torch.optim.Adam
+    tr.opt = cls(net.parameters(), lr=args.lr, betas=(args.beta1, args.beta2), eps=args.eps,
+                 weight_decay=args.weight_decay)
+    tr.opt.on_gpu = False
+
+
+def _check_resume_optimizer(args, path: str) -> None:
+    """--resume: results/optimizer.pth must be the state of the optimizer the run asks for."""
+    if not os.path.exists(path):
+        return
+    group = torch.load(path, weights_only=True)["param_groups"][0]
+    saved = ("adamw" if group.get("decoupled_weight_decay") else "adam") if "betas" in group else "sgd"
+    if saved != args.optimizer:
+        raise SystemExit(f"--resume: {path} holds the state of an {saved} optimizer, this run asks for --optimizer "
+                         f"{args.optimizer}")
+
+
 def _make_schedule(args, steps_per_epoch: int):
     """The --lr-schedule flags as an optim.LRSchedule over the whole run (None for ``constant``)."""
     from ..optim import LRSchedule
@@ -138,8 +194,10 @@ def single_main(argv=None) -> int:
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--resume", action="store_true", help="load results/model.pth + optimizer.pth first")
     _common_flags(ap)
+    _optimizer_flags(ap)
     args = ap.parse_args(argv)
     _check_ema_flag(args)
+    _check_optimizer_flags(args)
 
     torch.backends.cudnn.enabled = False  # ref src/train.py:20 (our kernels never use MIOpen)
     torch.manual_seed(args.seed)
@@ -168,13 +226,14 @@ def single_main(argv=None) -> int:
     ema_path = os.path.join(results, "ema.pth")
     sched = _make_schedule(args, (n_train + args.batch_size - 1) // args.batch_size)
     if args.resume:
+        _check_resume_optimizer(args, os.path.join(results, "optimizer.pth"))
         _restore_schedule(sched, sched_path)
 
     if use_fused:
         from .fused import FusedLeNetTrainer
 
         eng = FusedLeNetTrainer(net, train, lr=args.lr, momentum=args.momentum, global_batch=args.batch_size,
-                                compute_dtype=_dtype(args.dtype), seed=args.seed)
+                                compute_dtype=_dtype(args.dtype), seed=args.seed, **_optimizer_kw(args))
         opt_state = eng.optimizer_state_dict
         if args.resume:
             checkpoint.load_checkpoint(net, None, os.path.join(results, "model.pth"), None)
@@ -250,7 +309,8 @@ def single_main(argv=None) -> int:
     else:
         from .modular import ModularTrainer
 
-        tr = ModularTrainer(net, lr=args.lr, momentum=args.momentum)
+        tr = ModularTrainer(net, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
+        _modular_adam(args, tr, net)
         if args.resume:
             checkpoint.load_checkpoint(net, tr.opt, os.path.join(results, "model.pth"),
                                        os.path.join(results, "optimizer.pth"))
@@ -344,8 +404,10 @@ def dist_main(argv=None) -> int:
     ap.add_argument("--reference-metrics", action="store_true",
                     help="reproduce the reference's metric quirks (loss/bs sums, mean-of-batch-means val)")
     _common_flags(ap)
+    _optimizer_flags(ap)
     args = ap.parse_args(argv)
     _check_ema_flag(args)
+    _check_optimizer_flags(args)
 
     torch.backends.cudnn.enabled = False
     torch.manual_seed(args.seed)
@@ -384,7 +446,7 @@ def dist_main(argv=None) -> int:
         from .fused import FusedLeNetTrainer
 
         eng = FusedLeNetTrainer(net, train, lr=args.lr, momentum=args.momentum, global_batch=args.batch_size,
-                                ctx=ctx, compute_dtype=_dtype(args.dtype), seed=args.seed)
+                                ctx=ctx, compute_dtype=_dtype(args.dtype), seed=args.seed, **_optimizer_kw(args))
         sched = _make_schedule(args, -(-len(sampler) // per_rank))
         if sched is not None:  # (every rank the same table and position: the replicas stay bitwise identical)
             eng.set_lr_schedule(sched)
@@ -469,7 +531,9 @@ def dist_main(argv=None) -> int:
         from .modular import ModularTrainer
 
         tr = ModularTrainer(net, lr=args.lr, momentum=args.momentum, ctx=ctx, loss="ce",
-                            bucket_cap_mb=25.0 if args.bucket_mb is None else args.bucket_mb)
+                            bucket_cap_mb=25.0 if args.bucket_mb is None else args.bucket_mb,
+                            weight_decay=args.weight_decay)
+        _modular_adam(args, tr, net)
         loader = DeviceLoader(train, per_rank, sampler=sampler, device=dev,
                               dtype=ops.compute_dtype() if dev.type == "cuda" else torch.float32)
         sched = _make_schedule(args, len(loader))

@@ -170,8 +170,14 @@ UPDATE_FIELDS = ("slab", "grid", "vslab", "B", "grad_in", "grad_out", "params", 
                  "dampening", "weight_decay", "nesterov", "step", "ticket", "cursor", "rng_offset", "apply_sgd",
                  "loss_parts", "nparts", "loss_acc", "mfma_dtype", "dbg", "exch_id", "exch_timeout_s", "grad_post",
                  "fc_part", "lr_table", "lr_pos", "ema", "ema_decay")
+# What ``csed::lenet_update_adam`` (LenetStepper.set_update_adam) takes behind UPDATE_FIELDS: Adam's exp_avg_sq
+# and constants (exp_avg lives in ``momentum``); ``decoupled``: AdamW.
+ADAM_FIELDS = ("adam_v", "beta1", "beta2", "eps", "decoupled")
 TrainArgs = namedtuple("TrainArgs", TRAIN_FIELDS)
 UpdateArgs = namedtuple("UpdateArgs", UPDATE_FIELDS, defaults=(None, 0.0))  # (the moving average: off)
+AdamArgs = namedtuple("AdamArgs", ADAM_FIELDS)
+UpdateAdamArgs = namedtuple("UpdateAdamArgs", UPDATE_FIELDS + ADAM_FIELDS)  # (one lenet_update_adam launch)
+OPTIMIZERS = ("sgd", "adam", "adamw")
 _ENGINE = object()  # (default of a builder's ``cursor``: the engine's own device cursor)
 
 
@@ -188,7 +194,8 @@ class FusedLeNetTrainer:
                  compute_dtype: torch.dtype = torch.bfloat16, drop_p: float = 0.5, seed: int = 1,
                  grid: int | None = None, broadcast_init: bool = True, comm: bool | None = None,
                  split: bool | None = None, loopback_world: int = 0,
-                 reuse_exchange: "FusedLeNetTrainer | None" = None):
+                 reuse_exchange: "FusedLeNetTrainer | None" = None, optimizer: str = "sgd",
+                 betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8):
         import time
 
         _native.require()
@@ -226,6 +233,15 @@ class FusedLeNetTrainer:
         self.tile_staged = bool(geo.tile_staged)
         self.lr, self.momentum, self.dampening = float(lr), float(momentum), float(dampening)
         self.weight_decay, self.nesterov = float(weight_decay), bool(nesterov)
+        # "adam" / "adamw": the launches that apply the gradient run torch.optim.Adam's / AdamW's rule on the
+        # device (csed::lenet_update_adam) instead of SGD's; ``momentum``, ``dampening`` and ``nesterov`` are
+        # SGD's and are not passed then
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer {optimizer!r}: expected one of {OPTIMIZERS}")
+        self.optimizer = optimizer
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        if self.adam and (not all(0.0 <= b < 1.0 for b in self.betas) or not self.eps > 0.0):
+            raise ValueError(f"betas {betas} / eps {eps}: expected 0 <= beta < 1 and eps > 0")
         self.compute_dtype = compute_dtype
         self.drop_p = float(drop_p)
         self.seed = int(seed)  # masks decorrelate across ranks through the rank id in the element index
@@ -239,6 +255,9 @@ class FusedLeNetTrainer:
         if broadcast_init and self.world > 1:  # the DDP-constructor parameter sync (CS4)
             _comm.ctl_broadcast(self.ctx, self.flat.data, src=0)  # (RCCL, or the host over gloo)
         self.momentum_buf = _native.zeros(self.flat.data.shape, torch.float32, self.flat.data.device)
+        # Adam's exp_avg_sq (exp_avg lives in momentum_buf); the extension's own fill, like every buffer here
+        self.adam_v = (_native.zeros(self.flat.data.shape, torch.float32, self.flat.data.device)
+                       if self.adam else None)
         # zero-initialised: padding rows / columns of the images must stay zero
         self.wimg = _native.zeros(lay.wimg_elems, torch.int16, dev)
         # per-WG conv partial gradients and per-sample fc vectors (see lenet_fused.hip)
@@ -325,6 +344,11 @@ class FusedLeNetTrainer:
                 raise ValueError("loopback_world is a one-GPU measurement mode (world size 1)")
             self.exch = open_loopback_exchange(self.device, lay.exch_words, self.loopback_world)
             self.exchange_note = f"loopback exchange: {self.loopback_world} virtual ranks on one GPU"
+
+    @property
+    def adam(self) -> bool:
+        """Whether the engine trains with Adam / AdamW (``optimizer``) instead of SGD."""
+        return self.optimizer != "sgd"
 
     @property
     def grad_scale(self) -> float:
@@ -541,11 +565,12 @@ class FusedLeNetTrainer:
         in_kernel = self.fp32 if scale_in_kernel is None else scale_in_kernel
         fc_split = (reduces and exch is None) if fc_split is None else fc_split
         sch = self.lr_schedule if advances else None
+        sgd = not self.adam  # (SGD's own arguments are zero under Adam: the launcher insists)
         return UpdateArgs(
             slab=self.slab, grid=grid, vslab=self.vslab, B=B, grad_in=grad if mode == "apply" else None,
             grad_out=grad if mode == "reduce" else None, params=self.flat.data, momentum=self.momentum_buf,
-            wimg=self.wimg, lr=self.lr, mom=self.momentum, dampening=self.dampening, weight_decay=self.weight_decay,
-            nesterov=self.nesterov, step=self.step_count, ticket=self.ticket,
+            wimg=self.wimg, lr=self.lr, mom=self.momentum if sgd else 0.0, dampening=self.dampening if sgd else 0.0,
+            weight_decay=self.weight_decay, nesterov=self.nesterov and sgd, step=self.step_count, ticket=self.ticket,
             cursor=(self.cursor if cursor is _ENGINE else cursor) if advances else None,
             rng_offset=self.rng_offset if advances else None, apply_sgd=advances,
             loss_parts=self.loss_parts if loss else None, nparts=grid if loss else 0,
@@ -554,6 +579,19 @@ class FusedLeNetTrainer:
             grad_post=grad_scale if reduces and not in_kernel else 1.0, fc_part=self.fc_part if fc_split else None,
             lr_table=None if sch is None else sch.table, lr_pos=None if sch is None else sch.pos,
             ema=self.ema if advances else None, ema_decay=self.ema_decay if advances and self.ema is not None else 0.0)
+
+    def adam_args(self) -> AdamArgs:
+        """What a launch that applies Adam / AdamW takes behind update_args (ADAM_FIELDS)."""
+        return AdamArgs(adam_v=self.adam_v, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
+                        decoupled=self.optimizer == "adamw")
+
+    def update_launch(self, mode: str, **kw) -> tuple:
+        """The (name, arguments) launch of update_args(mode, ...): ``lenet_update``, or under Adam / AdamW, for
+        the modes that apply the gradient ("step" / "apply"), ``lenet_update_adam`` with adam_args behind."""
+        args = self.update_args(mode, **kw)
+        if self.adam and mode != "reduce":
+            return ("lenet_update_adam", UpdateAdamArgs(*args, *self.adam_args()))
+        return ("lenet_update", args)
 
     def update_plan(self, args: UpdateArgs) -> LenetUpdatePlan:
         """The plan of the ``csed::lenet_update`` launch that ``args`` (update_args) describes."""
@@ -578,10 +616,10 @@ class FusedLeNetTrainer:
         # full steps read the staged batch and stage the next one; the epoch's short tail uses perm
         train = ("lenet_train", self.train_args(perm=perm, stage_next=True, **kw))
         if self.exch is not None or not self.comm:  # one kernel: the fused exchange, or no exchange at all
-            return [train, ("lenet_update", self.update_args("step", **kw))]
+            return [train, self.update_launch("step", **kw)]
         g = self.flat.grad
-        return [train, ("lenet_update", self.update_args("reduce", grad=g, **kw)), ("all_reduce", (g,)),
-                ("lenet_update", self.update_args("apply", grad=g, **kw))]
+        return [train, self.update_launch("reduce", grad=g, **kw), ("all_reduce", (g,)),
+                self.update_launch("apply", grad=g, **kw)]
 
     def _tail_launches(self) -> list[tuple]:
         """The launches of the epoch's short last batch."""
@@ -656,7 +694,8 @@ class FusedLeNetTrainer:
         return ([self.flat.data, self.momentum_buf, self.wimg, self.step_count, self.cursor, self.rng_offset,
                  self.loss_acc] + ([self.xstage, self.lstage] if self.xstage is not None else [])
                 + ([self.lr_schedule.pos] if self.lr_schedule is not None else [])
-                + ([self.ema] if self.ema is not None else []))
+                + ([self.ema] if self.ema is not None else [])
+                + ([self.adam_v] if self.adam_v is not None else []))
 
     def _stamp(self, key: str, dt: float) -> None:
         self.bringup_s[key] = self.bringup_s.get(key, 0.0) + dt
@@ -721,12 +760,12 @@ class FusedLeNetTrainer:
         if self.comm and self.exch is None:
             return None
         # (the split-K fc scratch also next to the exchange, where the launcher does not use it)
-        train, update = self.train_args(stage_next=True), self.update_args("step", fc_split=True)
-        key = launch_key((train, update))
+        train, (name, update) = self.train_args(stage_next=True), self.update_launch("step", fc_split=True)
+        key = launch_key((train, name, update))
         if self._stepper is None or self._stepper[0] != key:
             st = torch.classes.csed.LenetStepper()
             st.set_train(*train)
-            st.set_update(*update)
+            (st.set_update_adam if name == "lenet_update_adam" else st.set_update)(*update)
             self._stepper = (key, st)
         return self._stepper[1]
 
@@ -817,8 +856,51 @@ class FusedLeNetTrainer:
         return out
 
     # ------------------------------------------------------------ optimizer io
+    def _adam_state_dict(self) -> dict:
+        """What torch.optim.Adam / AdamW (amsgrad=False) of this torch return: per parameter the step number
+        (a float32 scalar, theirs) and both moments, empty before the first step; one group."""
+        state = {}
+        t = int(self.step_count.item())
+        if t > 0:
+            for i in range(len(self.flat.params)):
+                state[i] = {"step": torch.tensor(float(t), dtype=torch.float32),
+                            "exp_avg": self.flat.view(self.momentum_buf, i).detach().cpu().clone(),
+                            "exp_avg_sq": self.flat.view(self.adam_v, i).detach().cpu().clone()}
+        lr = self.lr if self.lr_schedule is None else self.lr_schedule.current_lr()
+        group = {"lr": lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay,
+                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
+                 "differentiable": False, "fused": None, "decoupled_weight_decay": self.optimizer == "adamw",
+                 "params": list(range(len(self.flat.params)))}
+        return {"state": state, "param_groups": [group]}
+
+    def _load_adam_state_dict(self, sd: dict) -> None:
+        g = sd["param_groups"][0]
+        if "betas" not in g:
+            raise ValueError(f"this optimizer state is not Adam's (its group has {sorted(g)}): the engine trains "
+                             f"with {self.optimizer}")
+        if bool(g.get("decoupled_weight_decay", False)) != (self.optimizer == "adamw"):
+            raise ValueError(f"this optimizer state is {'AdamW' if g.get('decoupled_weight_decay') else 'Adam'}'s, "
+                             f"the engine trains with {self.optimizer}")
+        if g.get("amsgrad"):
+            raise ValueError("amsgrad optimizer states are not supported")
+        self.momentum_buf.zero_()
+        self.adam_v.zero_()
+        t = 0
+        for i in range(len(self.flat.params)):
+            st = sd.get("state", {}).get(i)
+            if st:
+                self.flat.view(self.momentum_buf, i).copy_(st["exp_avg"])
+                self.flat.view(self.adam_v, i).copy_(st["exp_avg_sq"])
+                t = int(st["step"])
+        self.step_count.fill_(t)  # (the bias corrections continue at the saved step)
+        self.lr, self.betas, self.eps = float(g["lr"]), (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"])
+        self.weight_decay = float(g["weight_decay"])
+        self.invalidate()
+
     def optimizer_state_dict(self) -> dict:
-        """torch.optim.SGD-compatible state dict (ref results/optimizer.pth)."""
+        """torch.optim.SGD-compatible state dict (ref results/optimizer.pth); under Adam / AdamW theirs."""
+        if self.adam:
+            return self._adam_state_dict()
         state = {}
         if int(self.step_count.item()) > 0 and self.momentum != 0:
             for i in range(len(self.flat.params)):
@@ -831,6 +913,8 @@ class FusedLeNetTrainer:
         return {"state": state, "param_groups": [group]}
 
     def load_optimizer_state_dict(self, sd: dict) -> None:
+        if self.adam:
+            return self._load_adam_state_dict(sd)
         have = False
         self.momentum_buf.zero_()
         for i in range(len(self.flat.params)):

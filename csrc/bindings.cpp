@@ -111,6 +111,28 @@ void check_ema(const char* op, const Tensor& params, const optional<Tensor>& ema
   TORCH_CHECK(ema_decay >= 0.0 && ema_decay < 1.0, op, ": ema_decay must be in [0, 1), got ", ema_decay);
 }
 
+// Adam / AdamW in place of SGD (csed::lenet_update_adam): exp_avg_sq, one fp32 value per parameter on their
+// device, and the rule's constants.  exp_avg lives in the momentum buffer, so SGD's own arguments must be zero.
+struct AdamOpt {
+  const Tensor& v; double beta1, beta2, eps; bool decoupled;
+};
+void check_adam(const char* op, const Tensor& params, const AdamOpt& ad, bool apply_sgd, double mom, double dampening,
+                bool nesterov) {
+  TORCH_CHECK(apply_sgd, op, ": Adam comes only with apply_sgd (a reduce-only launch changes no parameter)");
+  TORCH_CHECK(ad.v.is_cuda() && ad.v.device() == params.device(), op, ": adam_v must be on the parameters' device");
+  TORCH_CHECK(ad.v.scalar_type() == at::kFloat && ad.v.is_contiguous(), op, ": adam_v must be contiguous float32");
+  TORCH_CHECK(ad.v.numel() == params.numel(), op, ": adam_v must hold one value per parameter (", params.numel(),
+              "), got ", ad.v.numel());
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(ad.v.data_ptr()) & 15) == 0, op, ": adam_v must be 16-byte aligned");
+  TORCH_CHECK(ad.beta1 >= 0.0 && ad.beta1 < 1.0, op, ": beta1 must be in [0, 1), got ", ad.beta1);
+  TORCH_CHECK(ad.beta2 >= 0.0 && ad.beta2 < 1.0, op, ": beta2 must be in [0, 1), got ", ad.beta2);
+  TORCH_CHECK((float)ad.eps > 0.f, op, ": eps must be positive (in float32), got ", ad.eps);
+  TORCH_CHECK((float)ad.beta1 < 1.f && (float)ad.beta2 < 1.f, op, ": the betas must be below 1 in float32");
+  TORCH_CHECK(mom == 0.0 && dampening == 0.0 && !nesterov, op,
+              ": mom, dampening and nesterov are SGD's and must be 0 under Adam (got mom ", mom, ", dampening ",
+              dampening, ", nesterov ", nesterov, ")");
+}
+
 void sgd_flat(Tensor& p, const Tensor& g, Tensor& buf, double lr, double momentum, double dampening,
               double weight_decay, bool nesterov, double grad_scale, Tensor& step, Tensor& ticket,
               const optional<Tensor>& lr_table, const optional<Tensor>& lr_pos) {
@@ -855,7 +877,7 @@ csed::LenetUpdateArgs update_args(const Tensor& slab, int64_t grid, const Tensor
                                   int64_t mfma_dtype, const optional<Tensor>& dbg, int64_t exch_id,
                                   double exch_timeout_s, double grad_post, const optional<Tensor>& fc_part,
                                   const optional<Tensor>& lr_table, const optional<Tensor>& lr_pos,
-                                  const optional<Tensor>& ema, double ema_decay) {
+                                  const optional<Tensor>& ema, double ema_decay, const AdamOpt* adam = nullptr) {
   dev(slab, "slab"); dev(params, "params"); dev(momentum, "momentum"); dev(wimg, "wimg");
   TORCH_CHECK(params.numel() == csed::lenet_param_count() && momentum.numel() == params.numel(),
               "lenet_update: params / momentum must hold the 21840 flat LeNet parameters");
@@ -897,6 +919,12 @@ csed::LenetUpdateArgs update_args(const Tensor& slab, int64_t grid, const Tensor
   if (ema.has_value()) {
     a.ema = ema->data_ptr<float>(); a.ema_decay = (float)ema_decay;
   }
+  // Adam / AdamW in place of SGD (lenet_update_adam, set_update_adam)
+  if (adam) {
+    check_adam("lenet_update_adam", params, *adam, apply_sgd, mom, dampening, nesterov);
+    a.adam_v = adam->v.data_ptr<float>(); a.beta1 = (float)adam->beta1; a.beta2 = (float)adam->beta2;
+    a.adam_eps = (float)adam->eps; a.adam_decoupled = adam->decoupled ? 1 : 0;
+  }
   return a;
 }
 
@@ -923,6 +951,30 @@ void lenet_update(const Tensor& slab, int64_t grid, const Tensor& vslab, int64_t
       update_args(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
                   nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts, loss_acc, mfma_dtype, dbg,
                   exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos, ema, ema_decay);
+  csed::comm::IpcPeers px;
+  update_plan(a, &px);
+  CHECK_HIP(csed::launch_lenet_update(a, optpt<float>(loss_parts), (int)nparts, optpt<float>(loss_acc),
+                                      cur_stream(params), &px));
+}
+
+// lenet_update with Adam / AdamW in place of SGD: its arguments in order, then exp_avg_sq and the rule's
+// constants; exp_avg is ``momentum``.  The same builder, plan and launcher.
+void lenet_update_adam(const Tensor& slab, int64_t grid, const Tensor& vslab, int64_t B,
+                       const optional<Tensor>& grad_in, const optional<Tensor>& grad_out, Tensor& params,
+                       Tensor& momentum, Tensor& wimg, double lr, double mom, double dampening, double weight_decay,
+                       bool nesterov, Tensor& step, Tensor& ticket, const optional<Tensor>& cursor,
+                       const optional<Tensor>& rng_offset, bool apply_sgd, const optional<Tensor>& loss_parts,
+                       int64_t nparts, const optional<Tensor>& loss_acc, int64_t mfma_dtype,
+                       const optional<Tensor>& dbg, int64_t exch_id, double exch_timeout_s, double grad_post,
+                       const optional<Tensor>& fc_part, const optional<Tensor>& lr_table,
+                       const optional<Tensor>& lr_pos, const optional<Tensor>& ema, double ema_decay, Tensor& adam_v,
+                       double beta1, double beta2, double eps, bool decoupled) {
+  const c10::DeviceGuard gd(params.device());
+  const AdamOpt ad{adam_v, beta1, beta2, eps, decoupled};
+  const csed::LenetUpdateArgs a =
+      update_args(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
+                  nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts, loss_acc, mfma_dtype, dbg,
+                  exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos, ema, ema_decay, &ad);
   csed::comm::IpcPeers px;
   update_plan(a, &px);
   CHECK_HIP(csed::launch_lenet_update(a, optpt<float>(loss_parts), (int)nparts, optpt<float>(loss_acc),
@@ -1073,11 +1125,43 @@ struct LenetStepper : torch::CustomClassHolder {
                   int64_t nparts_, optional<Tensor> loss_acc_t, int64_t mfma_dtype, optional<Tensor> dbg,
                   int64_t exch_id, double exch_timeout_s, double grad_post, optional<Tensor> fc_part,
                   optional<Tensor> lr_table, optional<Tensor> lr_pos, optional<Tensor> ema, double ema_decay) {
+    set_update_impl(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
+                    nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts_t, nparts_, loss_acc_t,
+                    mfma_dtype, dbg, exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos, ema, ema_decay,
+                    nullptr);
+  }
+
+  // set_update with Adam / AdamW in place of SGD (csed::lenet_update_adam's argument list); run() replays
+  // whichever update was set last.
+  void set_update_adam(Tensor slab, int64_t grid, Tensor vslab, int64_t B, optional<Tensor> grad_in,
+                       optional<Tensor> grad_out, Tensor params, Tensor momentum, Tensor wimg, double lr, double mom,
+                       double dampening, double weight_decay, bool nesterov, Tensor step, Tensor ticket,
+                       optional<Tensor> cursor, optional<Tensor> rng_offset, bool apply_sgd,
+                       optional<Tensor> loss_parts_t, int64_t nparts_, optional<Tensor> loss_acc_t, int64_t mfma_dtype,
+                       optional<Tensor> dbg, int64_t exch_id, double exch_timeout_s, double grad_post,
+                       optional<Tensor> fc_part, optional<Tensor> lr_table, optional<Tensor> lr_pos,
+                       optional<Tensor> ema, double ema_decay, Tensor adam_v, double beta1, double beta2, double eps,
+                       bool decoupled) {
+    const AdamOpt ad{adam_v, beta1, beta2, eps, decoupled};
+    set_update_impl(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
+                    nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts_t, nparts_, loss_acc_t,
+                    mfma_dtype, dbg, exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos, ema, ema_decay,
+                    &ad);
+  }
+
+  void set_update_impl(Tensor& slab, int64_t grid, Tensor& vslab, int64_t B, optional<Tensor>& grad_in,
+                       optional<Tensor>& grad_out, Tensor& params, Tensor& momentum, Tensor& wimg, double lr,
+                       double mom, double dampening, double weight_decay, bool nesterov, Tensor& step, Tensor& ticket,
+                       optional<Tensor>& cursor, optional<Tensor>& rng_offset, bool apply_sgd,
+                       optional<Tensor>& loss_parts_t, int64_t nparts_, optional<Tensor>& loss_acc_t,
+                       int64_t mfma_dtype, optional<Tensor>& dbg, int64_t exch_id, double exch_timeout_s,
+                       double grad_post, optional<Tensor>& fc_part, optional<Tensor>& lr_table,
+                       optional<Tensor>& lr_pos, optional<Tensor>& ema, double ema_decay, const AdamOpt* adam) {
     TORCH_CHECK(apply_sgd && !grad_in && !grad_out && cursor, "LenetStepper: set_update takes a full step at a cursor");
     const csed::LenetUpdateArgs a =
         update_args(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
                     nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts_t, loss_acc_t, mfma_dtype, dbg,
-                    exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos, ema, ema_decay);
+                    exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos, ema, ema_decay, adam);
     csed::comm::IpcPeers peers;
     update_plan(a, &peers);  // the exchange's view and the plan's error once, here: a bad block never reaches run()
     ua = a;
@@ -1086,7 +1170,8 @@ struct LenetStepper : torch::CustomClassHolder {
     loss_acc = optpt<float>(loss_acc_t);
     nparts = nparts_;
     keep_u = {slab,   vslab,      params,       momentum,   wimg, step,   ticket,
-              cursor, rng_offset, loss_parts_t, loss_acc_t, dbg,  fc_part, lr_table, lr_pos, ema};
+              cursor, rng_offset, loss_parts_t, loss_acc_t, dbg,  fc_part, lr_table, lr_pos, ema,
+              adam ? optional<Tensor>(adam->v) : optional<Tensor>()};
   }
 
   void run(int64_t k) {
@@ -1116,6 +1201,7 @@ TORCH_LIBRARY(csed, m) {
       .def(torch::init<>())
       .def("set_train", &LenetStepper::set_train)
       .def("set_update", &LenetStepper::set_update)
+      .def("set_update_adam", &LenetStepper::set_update_adam)
       .def("run", &LenetStepper::run);
   m.def("lenet_layout() -> int[]", &lenet_layout);
   m.def("lenet_plan(int B, int grid, int mfma_dtype, int kernel, bool staged, bool stage_next, bool cursor, bool train) "
@@ -1150,6 +1236,13 @@ TORCH_LIBRARY(csed, m) {
         "Tensor(j!)? dbg=None, int exch_id=-1, float exch_timeout_s=2.0, float grad_post=1.0, "
         "Tensor(k!)? fc_part=None, Tensor? lr_table=None, Tensor(l!)? lr_pos=None, Tensor(m!)? ema=None, "
         "float ema_decay=0.0) -> ()");
+  m.def("lenet_update_adam(Tensor slab, int grid, Tensor vslab, int B, Tensor? grad_in, Tensor(a!)? grad_out, "
+        "Tensor(b!) params, Tensor(c!) momentum, Tensor(d!) wimg, float lr, float mom, float dampening, "
+        "float weight_decay, bool nesterov, Tensor(e!) step, Tensor(f!) ticket, Tensor(g!)? cursor, "
+        "Tensor(h!)? rng_offset, bool apply_sgd, Tensor? loss_parts, int nparts, Tensor(i!)? loss_acc, int mfma_dtype, "
+        "Tensor(j!)? dbg, int exch_id, float exch_timeout_s, float grad_post, Tensor(k!)? fc_part, Tensor? lr_table, "
+        "Tensor(l!)? lr_pos, Tensor(m!)? ema, float ema_decay, Tensor(n!) adam_v, float beta1, float beta2, float eps, "
+        "bool decoupled) -> ()");  // (no defaults: the Adam arguments follow positionally)
   m.def("lenet_eval(Tensor images, Tensor labels, Tensor order, int n, Tensor wimg, Tensor params, float mean, "
         "float std, Tensor(a!) out_parts, Tensor(b!)? logp_out, int mfma_dtype, int kernel=0) -> ()");
   m.def("gather_normalize(Tensor src, Tensor idx, Tensor? cursor, int B, float mean, float std, Tensor(a!) out, "
@@ -1229,6 +1322,7 @@ TORCH_LIBRARY_IMPL(csed, CUDA, m) {
   m.impl("lenet_pack", &lenet_pack);
   m.impl("lenet_train", &lenet_train);
   m.impl("lenet_update", &lenet_update);
+  m.impl("lenet_update_adam", &lenet_update_adam);
   m.impl("lenet_stage", &lenet_stage);
   m.impl("lenet_eval", &lenet_eval);
 }

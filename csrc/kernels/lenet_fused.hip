@@ -52,6 +52,7 @@
 //   conv1.w 0, conv1.b 250, conv2.w 260, conv2.b 5260, fc1.w 5280,
 //   fc1.b 21280, fc2.w 21330, fc2.b 21830.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <type_traits>
 
@@ -1427,28 +1428,64 @@ __global__ void __launch_bounds__(512) lenet_stage_kernel(LenetStageArgs st, con
   gather_batch(st, cursor ? cursor[0] : 0, rows_sh);
 }
 
+// Adam's per-launch scalars, the same in every lane: lr / (1 - beta1^t) and sqrt(1 - beta2^t), t = step[0] + 1.
+struct AdamStep { float step_size, bc2_sqrt; };
+
+// 1 - beta^t from lb = log(beta) (formed on the host in double, LenetUpdateArgs::adam_lb1 / 2): at small t
+// the difference cancels (beta2 = 0.999, t = 1: 1e-3), and 1.f - powf(beta, t) would keep powf's absolute
+// error of an ulp of 1, i.e. 1e3 ulps of the result.  -expm1f(t * lb) has the relative error of lb, of the
+// product and of expm1f (|x e^x / (e^x - 1)| <= 1 for x < 0, so the argument's error is not amplified).
+// beta = 0: lb = -inf, expm1f(-inf) = -1.  t is exact in fp32 below 2^24 steps.
+__device__ __forceinline__ AdamStep adam_step(const LenetUpdateArgs& a, float lr, uint32_t step_lo) {
+  const float t = (float)(step_lo + 1u);
+  AdamStep k;
+  k.step_size = lr / -expm1f(t * a.adam_lb1);
+  k.bc2_sqrt = sqrtf(-expm1f(t * a.adam_lb2));
+  return k;
+}
+
+// torch.optim.Adam / AdamW (amsgrad = False, maximize = False) of one element, in fp32, every fused
+// multiply-add spelled out so that each instantiation rounds alike: g the final gradient, p / m / v the
+// parameter, exp_avg and exp_avg_sq (in: old, out: new).
+__device__ __forceinline__ void adam_rule(const LenetUpdateArgs& a, float g, float& p, float& m, float& v, float lr,
+                                          AdamStep k) {
+  if (a.adam_decoupled) p = p * fmaf(-lr, a.weight_decay, 1.f);
+  else g = fmaf(a.weight_decay, p, g);
+  m = fmaf(1.f - a.beta1, g - m, m);
+  v = fmaf(1.f - a.beta2, g * g, a.beta2 * v);
+  p = fmaf(-k.step_size, m / (sqrtf(v) / k.bc2_sqrt + a.adam_eps), p);
+}
+
 // Final consumer of one parameter's gradient: export or SGD step.  p / m are
 // params[i] / momentum[i], loaded by the caller at kernel entry so their
 // round trip overlaps the gradient loads instead of following them.  lr: the launch's learning
 // rate (a.lr, or the caller's entry of the device-resident schedule).  EMA (a.ema set: the launcher's
 // choice of instantiation): e is the parameter's old moving average ema[i], loaded by the caller with
-// p / m; the new one, e + (1 - decay) * (p_new - e), is stored after the parameter.
-template <typename T, bool EMA>
+// p / m; the new one, e + (1 - decay) * (p_new - e), is stored after the parameter.  ADAM (a.adam_v set,
+// likewise an instantiation): Adam's rule instead of SGD's (adam_rule), from the old exp_avg_sq v = adam_v[i]
+// loaded with p / m and the launch's bias-correction terms k; m is exp_avg.
+template <typename T, bool EMA, bool ADAM>
 __device__ __forceinline__ void finish_param(const LenetUpdateArgs& a, int i, float gsum, bool first, float p,
-                                             float m, int d0, int d1, float lr, float e) {
+                                             float m, int d0, int d1, float lr, float e, float v, AdamStep k) {
   if (!a.apply_sgd) {
     a.grad_out[i] = gsum;
     return;
   }
   if (a.grad_out) a.grad_out[i] = gsum;
-  const float gj = gsum + a.weight_decay * p;
-  float d = gj;
-  if (a.mom != 0.f) {
-    const float bj = first ? gj : fmaf(a.mom, m, (1.f - a.dampening) * gj);
-    a.momentum[i] = bj;
-    d = a.nesterov ? fmaf(a.mom, bj, gj) : bj;
+  if constexpr (ADAM) {
+    adam_rule(a, gsum, p, m, v, lr, k);
+    a.momentum[i] = m;
+    a.adam_v[i] = v;
+  } else {
+    const float gj = gsum + a.weight_decay * p;
+    float d = gj;
+    if (a.mom != 0.f) {
+      const float bj = first ? gj : fmaf(a.mom, m, (1.f - a.dampening) * gj);
+      a.momentum[i] = bj;
+      d = a.nesterov ? fmaf(a.mom, bj, gj) : bj;
+    }
+    p = fmaf(-lr, d, p);
   }
-  p = fmaf(-lr, d, p);
   a.params[i] = p;
   write_slots<T>(a.wimg, d0, d1, p);
   if constexpr (EMA) a.ema[i] = fmaf(1.f - a.ema_decay, p - e, e);
@@ -1457,27 +1494,33 @@ __device__ __forceinline__ void finish_param(const LenetUpdateArgs& a, int i, fl
 // finish_param for 4 consecutive fc1 weights i .. i+3 (16-byte aligned; their weight-image
 // slots d0 .. d0+3 are consecutive and 8-byte aligned): the same arithmetic per element,
 // one wide store per array instead of four
-template <typename T, bool EMA>
+template <typename T, bool EMA, bool ADAM>
 __device__ __forceinline__ void finish_param4(const LenetUpdateArgs& a, int i, float4 gsum, bool first, float4 p4,
-                                              float4 m4, int d0, float lr, float4 e4) {
+                                              float4 m4, int d0, float lr, float4 e4, float4 v4, AdamStep k) {
   float gv[4] = {gsum.x, gsum.y, gsum.z, gsum.w}, pv[4] = {p4.x, p4.y, p4.z, p4.w}, mv[4] = {m4.x, m4.y, m4.z, m4.w};
   float ev[4] = {e4.x, e4.y, e4.z, e4.w};
+  float vv[4] = {v4.x, v4.y, v4.z, v4.w};
   if (!a.apply_sgd || a.grad_out) *reinterpret_cast<float4*>(a.grad_out + i) = gsum;
   if (!a.apply_sgd) return;
   u16x4 h;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const float gj = gv[j] + a.weight_decay * pv[j];
-    float d = gj;
-    if (a.mom != 0.f) {
-      const float bj = first ? gj : fmaf(a.mom, mv[j], (1.f - a.dampening) * gj);
-      mv[j] = bj;
-      d = a.nesterov ? fmaf(a.mom, bj, gj) : bj;
+    if constexpr (ADAM) {
+      adam_rule(a, gv[j], pv[j], mv[j], vv[j], lr, k);
+    } else {
+      const float gj = gv[j] + a.weight_decay * pv[j];
+      float d = gj;
+      if (a.mom != 0.f) {
+        const float bj = first ? gj : fmaf(a.mom, mv[j], (1.f - a.dampening) * gj);
+        mv[j] = bj;
+        d = a.nesterov ? fmaf(a.mom, bj, gj) : bj;
+      }
+      pv[j] = fmaf(-lr, d, pv[j]);
     }
-    pv[j] = fmaf(-lr, d, pv[j]);
     if constexpr (!std::is_same<T, float>::value) h[j] = h16<T>(as_stored<T>(pv[j]));
   }
-  if (a.mom != 0.f) *reinterpret_cast<float4*>(a.momentum + i) = make_float4(mv[0], mv[1], mv[2], mv[3]);
+  if (ADAM || a.mom != 0.f) *reinterpret_cast<float4*>(a.momentum + i) = make_float4(mv[0], mv[1], mv[2], mv[3]);
+  if constexpr (ADAM) *reinterpret_cast<float4*>(a.adam_v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
   *reinterpret_cast<float4*>(a.params + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
   if constexpr (!std::is_same<T, float>::value) *reinterpret_cast<u16x4*>(a.wimg + d0) = h;
   if constexpr (EMA) {
@@ -1742,8 +1785,9 @@ __device__ __forceinline__ void ll_poll(const comm::IpcPeers& px, const XPtrs<R>
 // (2, 4 or 8 >= px.world).  SCHED: the learning rate comes from the device-resident schedule
 // (a.lr_table / a.lr_pos) -- its own instantiations, so a launch without a table runs the code it
 // ran before the schedule existed: no load, no barrier, no ticket.  EMA: the launch keeps the parameters'
-// moving average (a.ema set) -- likewise its own instantiations (see launch_lenet_update).
-template <typename T, int XW, bool LBC = false, bool SCHED = false, bool EMA = false>
+// moving average (a.ema set) -- likewise its own instantiations (see launch_lenet_update).  ADAM: the
+// launch applies Adam / AdamW instead of SGD (a.adam_v set), again its own instantiations.
+template <typename T, int XW, bool LBC = false, bool SCHED = false, bool EMA = false, bool ADAM = false>
 __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ vslab, int B, float* loss_parts,
                             int nparts, float* loss_acc, const comm::IpcPeers& px, uint64_t timeout_ticks, int blk,
                             int nblk, int tid, float4* part_, float* part2_, int fc_tpb, int fc_sl_arg) {
@@ -1809,6 +1853,19 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
       return a.lr;
     }
   };
+  // Adam's step number t = step[0] + 1: every block reads step[0] here, before it takes its ticket (the
+  // last ticket advances it).  Its low dword, a per-lane load through opaque(0) like the tag and the
+  // position: only the bias corrections need it, where the gradient is final (adam_now).
+  const uint32_t step_raw = ADAM ? ((gcptr32u)a.step)[opaque(0)] : 0u;
+  auto adam_now = [&](float lr) {
+    AdamStep k{0.f, 0.f};
+    if constexpr (ADAM) {
+      uint32_t v = step_raw;
+      asm volatile("" : "+v"(v));
+      k = adam_step(a, lr, v);
+    }
+    return k;
+  };
   bool timed_out = false;
 #define USTAMP(k) \
   if (a.dbg && tid == 0 && blk < a.dbg_blocks) a.dbg[blk * 8 + (k)] = __builtin_amdgcn_s_memrealtime();
@@ -1836,13 +1893,14 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
     // the half's first wave owns slab slots pbc*64 + ht (16 float4 columns) = parameter pi
     // (-1: padding slot): prefetch p / m now
     const int pi = slot_param(pbc * (UP_C * 4) + min(ht, 63));
-    float p0 = 0.f, m0 = 0.f, e0 = 0.f;
+    float p0 = 0.f, m0 = 0.f, e0 = 0.f, v0 = 0.f;
     int d0 = -1, d1 = -1;
     auto pm_loads = [&]() {
       if (a.apply_sgd && ht < 64) {
         p0 = a.params[max(pi, 0)];
         m0 = a.momentum[max(pi, 0)];
         if constexpr (EMA) e0 = a.ema[max(pi, 0)];  // (the old average rides with p / m)
+        if constexpr (ADAM) v0 = a.adam_v[max(pi, 0)];  // (and Adam's exp_avg_sq)
       }
       image_slots_flat(max(pi, 0), d0, d1);  // (lanes without a parameter store nothing)
     };
@@ -1917,7 +1975,8 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
         ll_poll<1, XR, LBC>(px, xp, tag_now(), pbc * (UP_C * 4) + ht, live, g, timeout_ticks, timed_out,
                        a.dbg && tid == 0 && blk < a.dbg_blocks ? a.dbg + blk * 8 : nullptr, blk);
       }
-      finish_param<T, EMA>(a, pi, g[0], first, p0, m0, d0, d1, lr_now(), e0);
+      const float lr = lr_now();
+      finish_param<T, EMA, ADAM>(a, pi, g[0], first, p0, m0, d0, d1, lr, e0, v0, adam_now(lr));
     }
     USTAMP(4);
     if (pb == 0 && loss_parts && tid < 64) {
@@ -1973,6 +2032,7 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
     int pidx[4];
     float pp[4] = {0.f, 0.f, 0.f, 0.f}, pm[4] = {0.f, 0.f, 0.f, 0.f};
     float pe[4] = {0.f, 0.f, 0.f, 0.f};  // their old moving averages (EMA)
+    float pq[4] = {0.f, 0.f, 0.f, 0.f};  // their old exp_avg_sq (ADAM)
     // fc1 weight tiles (wave-uniform) finish in row layout: lane = (row, 4 columns), one
     // float4 per array (finish_param4); the others per element in the MFMA layout
     const bool vec = live_tile && fc1 && nt < 20;
@@ -1989,6 +2049,7 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
         pp[r] = a.params[max(pidx[r], 0)];
         pm[r] = a.momentum[max(pidx[r], 0)];
         if constexpr (EMA) pe[r] = a.ema[max(pidx[r], 0)];
+        if constexpr (ADAM) pq[r] = a.adam_v[max(pidx[r], 0)];
       }
     }
     if (a.apply_sgd && sub == 0 && fin && vec) {
@@ -1999,6 +2060,10 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
       if constexpr (EMA) {
         const float4 e4 = *reinterpret_cast<const float4*>(a.ema + vidx);
         pe[0] = e4.x; pe[1] = e4.y; pe[2] = e4.z; pe[3] = e4.w;
+      }
+      if constexpr (ADAM) {
+        const float4 q4 = *reinterpret_cast<const float4*>(a.adam_v + vidx);
+        pq[0] = q4.x; pq[1] = q4.y; pq[2] = q4.z; pq[3] = q4.w;
       }
     }
     // fc destinations in the weight images (no table lookups for fc)
@@ -2184,6 +2249,7 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
     asm volatile("" ::"v"(pp[0]), "v"(pp[1]), "v"(pp[2]), "v"(pp[3]), "v"(pm[0]), "v"(pm[1]), "v"(pm[2]),
                  "v"(pm[3]));
     if constexpr (EMA) asm volatile("" ::"v"(pe[0]), "v"(pe[1]), "v"(pe[2]), "v"(pe[3]));  // (and the old averages)
+    if constexpr (ADAM) asm volatile("" ::"v"(pq[0]), "v"(pq[1]), "v"(pq[2]), "v"(pq[3]));  // (and exp_avg_sq)
     // fixed-order combine of the tile's wpt partials (reuses the CONV role's LDS)
     float* pfc = reinterpret_cast<float*>(part_);
     if (wpt > 1) {  // uniform
@@ -2269,12 +2335,17 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
                 const float4 e4 = *reinterpret_cast<const float4*>(a.ema + vidx);
                 pe[0] = e4.x; pe[1] = e4.y; pe[2] = e4.z; pe[3] = e4.w;
               }
+              if constexpr (ADAM) {
+                const float4 q4 = *reinterpret_cast<const float4*>(a.adam_v + vidx);
+                pq[0] = q4.x; pq[1] = q4.y; pq[2] = q4.z; pq[3] = q4.w;
+              }
             } else {
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
                 pp[r] = a.params[max(pidx[r], 0)];
                 pm[r] = a.momentum[max(pidx[r], 0)];
                 if constexpr (EMA) pe[r] = a.ema[max(pidx[r], 0)];
+                if constexpr (ADAM) pq[r] = a.adam_v[max(pidx[r], 0)];
               }
             }
           }
@@ -2291,6 +2362,7 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
       }
       if (do_fin) {
       const float lr = lr_now();
+      const AdamStep ak = adam_now(lr);
       if (vec) {
         // MFMA layout (row 4kq + r, column l16) -> row layout through this wave's LDS slot
         float* tr = pfc + wave * 256;
@@ -2299,13 +2371,15 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
         __builtin_amdgcn_wave_barrier();
         const float4 gv = *reinterpret_cast<const float4*>(tr + (lane >> 2) * 16 + 4 * (lane & 3));
         if (vrow < 50)
-          finish_param4<T, EMA>(a, vidx, gv, first, make_float4(pp[0], pp[1], pp[2], pp[3]),
-                           make_float4(pm[0], pm[1], pm[2], pm[3]), I_F1 + vrow * LD_F1 + vcol, lr,
-                           make_float4(pe[0], pe[1], pe[2], pe[3]));
+          finish_param4<T, EMA, ADAM>(a, vidx, gv, first, make_float4(pp[0], pp[1], pp[2], pp[3]),
+                                      make_float4(pm[0], pm[1], pm[2], pm[3]), I_F1 + vrow * LD_F1 + vcol, lr,
+                                      make_float4(pe[0], pe[1], pe[2], pe[3]),
+                                      make_float4(pq[0], pq[1], pq[2], pq[3]), ak);
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (pidx[r] >= 0) finish_param<T, EMA>(a, pidx[r], g[r], first, pp[r], pm[r], fd[r], -1, lr, pe[r]);
+          if (pidx[r] >= 0)
+            finish_param<T, EMA, ADAM>(a, pidx[r], g[r], first, pp[r], pm[r], fd[r], -1, lr, pe[r], pq[r], ak);
       }
       }  // do_fin
       USTAMP(4);
@@ -2320,10 +2394,11 @@ __device__ void update_role(const LenetUpdateArgs& a, const float* __restrict__ 
   if (a.apply_sgd) {
     // Device counters.  cursor / rng_offset are never read by this kernel, so
     // one thread bumps them directly.  step[0] is read by every block only when
-    // dampening != 0, the schedule's position by every block of a SCHED launch; then the last
+    // dampening != 0 and by every block of an ADAM launch (its step number), the schedule's position by
+    // every block of a SCHED launch; then the last
     // block to take a ticket bumps them (bumped by block 0 as soon as it is done, a block that
     // starts later would read the next step's value).
-    if (SCHED || a.dampening != 0.f) {
+    if (SCHED || ADAM || a.dampening != 0.f) {
       __syncthreads();
       if (tid == 0) {
         const int t = atomicAdd(a.ticket, 1);  // every block read step[0] / lr_pos[0] before this
@@ -2348,7 +2423,7 @@ struct UpdateKargs {
   LenetUpdateArgs a; const float* vslab; int B; float* loss_parts; int nparts; float* loss_acc;
   uint64_t timeout_ticks; int fc_tpb; int fc_sl;
 };
-template <typename T, int XW, bool LBC = false, bool SCHED = false, bool EMA = false>
+template <typename T, int XW, bool LBC = false, bool SCHED = false, bool EMA = false, bool ADAM = false>
 __global__ void __launch_bounds__(UP_NT) lenet_update_kernel(LenetUpdateArgs a, const float* __restrict__ vslab,
                                                              int B, float* loss_parts, int nparts,
                                                              float* loss_acc, uint64_t timeout_ticks, int fc_tpb,
@@ -2356,26 +2431,30 @@ __global__ void __launch_bounds__(UP_NT) lenet_update_kernel(LenetUpdateArgs a, 
   prefetch_kernargs<sizeof(UpdateKargs) + sizeof(comm::IpcPeers)>();  // (+ gridDim.x after px)
   __shared__ float4 part[UP_S][UP_C];
   __shared__ float part2[4][UP_C * 4];
-  update_role<T, XW, LBC, SCHED, EMA>(a, vslab, B, loss_parts, nparts, loss_acc, px, timeout_ticks, blockIdx.x, gridDim.x,
-                              threadIdx.x, &part[0][0], &part2[0][0], fc_tpb, fc_sl);
+  update_role<T, XW, LBC, SCHED, EMA, ADAM>(a, vslab, B, loss_parts, nparts, loss_acc, px, timeout_ticks, blockIdx.x,
+                                            gridDim.x, threadIdx.x, &part[0][0], &part2[0][0], fc_tpb, fc_sl);
 }
 
 // SGD from an already-reduced gradient (DDP: after the all-reduce).  SCHED: at the schedule's
-// learning rate (see update_role; a uniform load here: nothing is in flight that it could delay).
-template <typename T, bool SCHED = false, bool EMA = false>
+// learning rate (see update_role; a uniform load here: nothing is in flight that it could delay).  ADAM:
+// Adam / AdamW at step number step[0] + 1, read by every block before its ticket.
+template <typename T, bool SCHED = false, bool EMA = false, bool ADAM = false>
 __global__ void lenet_sgd_kernel(LenetUpdateArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool first = (a.step && a.dampening != 0.f) ? a.step[0] == 0 : false;
   float lr = a.lr;
   if constexpr (SCHED) lr = a.lr_table[min(max(a.lr_pos[0], (int64_t)0), (int64_t)a.lr_len - 1)];
+  AdamStep ak{0.f, 0.f};
+  if constexpr (ADAM) ak = adam_step(a, lr, (uint32_t)a.step[0]);
   if (i < NP) {
     int d0, d1;
     image_slots(i, d0, d1);
-    float e = 0.f;
+    float e = 0.f, v = 0.f;
     if constexpr (EMA) e = a.ema[i];
-    finish_param<T, EMA>(a, i, a.grad_in[i], first, a.params[i], a.momentum[i], d0, d1, lr, e);
+    if constexpr (ADAM) v = a.adam_v[i];
+    finish_param<T, EMA, ADAM>(a, i, a.grad_in[i], first, a.params[i], a.momentum[i], d0, d1, lr, e, v, ak);
   }
-  if (SCHED || a.dampening != 0.f) {
+  if (SCHED || ADAM || a.dampening != 0.f) {
     __syncthreads();
     if (threadIdx.x == 0) {
       const int t = atomicAdd(a.ticket, 1);
@@ -2440,8 +2519,22 @@ int lenet_forced_fc_slices() {
 
 // Runs what lenet_update_plan (kernels/lenet_plan.h) decides: lenet_sgd_kernel on grad_in, or
 // lenet_update_kernel in the plan's (XW, LBC, SCHED) instantiation, on its grid, with its trailing arguments.
-hipError_t launch_lenet_update(const LenetUpdateArgs& a, float* loss_parts, int nparts, float* loss_acc,
+hipError_t launch_lenet_update(const LenetUpdateArgs& a_in, float* loss_parts, int nparts, float* loss_acc,
                                hipStream_t s, const comm::IpcPeers* px_cached) {
+  // Adam / AdamW is no plan dimension either: a template flag chosen here from a.adam_v != nullptr, like the
+  // moving average below and for its reason.  It replaces SGD's rule, so it comes with apply_sgd, reads
+  // step[0] in every block (hence the ticket) and leaves SGD's own arguments no meaning: they must be zero.
+  // The kernels get log(beta) from here, in double (adam_step).
+  LenetUpdateArgs a = a_in;
+  a.adam_lb1 = a.adam_lb2 = 0.f;
+  if (a.adam_v) {
+    const bool betas = a.beta1 >= 0.f && a.beta1 < 1.f && a.beta2 >= 0.f && a.beta2 < 1.f;
+    if (!a.apply_sgd || !a.step || !a.ticket || ((uintptr_t)a.adam_v & 15) || !betas || !(a.adam_eps > 0.f) ||
+        a.mom != 0.f || a.dampening != 0.f || a.nesterov != 0)
+      return hipErrorInvalidValue;
+    a.adam_lb1 = (float)std::log((double)a.beta1);
+    a.adam_lb2 = (float)std::log((double)a.beta2);
+  }
   static_assert(NB_UPDATE <= comm::kIpcMaxBlocks, "one exchange counter per update workgroup");
   comm::IpcPeers px{};
   if (a.exch_id >= 0) {
@@ -2462,23 +2555,33 @@ hipError_t launch_lenet_update(const LenetUpdateArgs& a, float* loss_parts, int 
   if (a.ema && (!a.apply_sgd || !(a.ema_decay >= 0.f && a.ema_decay < 1.f) || ((uintptr_t)a.ema & 15)))
     return hipErrorInvalidValue;
   if (p.form == kUpdateSgd) {
+#define CSED_SGD_PICK(A)                                                                                             \
+  kern = a.ema ? (p.sched ? lenet_sgd_kernel<scalar_t, true, true, A> : lenet_sgd_kernel<scalar_t, false, true, A>) \
+               : (p.sched ? lenet_sgd_kernel<scalar_t, true, false, A> : lenet_sgd_kernel<scalar_t, false, false, A>)
     CSED_DISPATCH_UPDATE(a.mfma_dtype, {
-      void (*kern)(LenetUpdateArgs) =
-          a.ema ? (p.sched ? lenet_sgd_kernel<scalar_t, true, true> : lenet_sgd_kernel<scalar_t, false, true>)
-                : (p.sched ? lenet_sgd_kernel<scalar_t, true> : lenet_sgd_kernel<scalar_t, false>);
+      void (*kern)(LenetUpdateArgs) = nullptr;
+      if (a.adam_v) CSED_SGD_PICK(true);
+      else CSED_SGD_PICK(false);
       hipLaunchKernelGGL(kern, dim3(p.blocks), dim3(256), 0, s, a);
     });
+#undef CSED_SGD_PICK
     return hipGetLastError();
   }
   const uint64_t ticks = p.form == kUpdateExchange ? (uint64_t)(a.exch_timeout_s * 1e8) : 0;  // s_memrealtime: 100 MHz
   // The (XW, LBC, SCHED) instantiations that occur: the exchange's world bound 2 / 4 / 8, looped back (its
-  // invariant check) or not, and XW = 0 without one; each with and without the schedule.
+  // invariant check) or not, and XW = 0 without one; each with and without the schedule, the moving average
+  // and Adam.
   void (*kern)(LenetUpdateArgs, const float*, int, float*, int, float*, uint64_t, int, int, comm::IpcPeers) = nullptr;
-#define CSED_UPDATE_PICK(W, L)               \
-  if (p.world_bound == W && p.loopback == L) \
-  kern = a.ema ? (p.sched ? lenet_update_kernel<scalar_t, W, L, true, true>                \
-                          : lenet_update_kernel<scalar_t, W, L, false, true>)              \
-               : (p.sched ? lenet_update_kernel<scalar_t, W, L, true> : lenet_update_kernel<scalar_t, W, L, false>)
+#define CSED_UPDATE_PICK_A(W, L, A)                                                  \
+  kern = a.ema ? (p.sched ? lenet_update_kernel<scalar_t, W, L, true, true, A>       \
+                          : lenet_update_kernel<scalar_t, W, L, false, true, A>)     \
+               : (p.sched ? lenet_update_kernel<scalar_t, W, L, true, false, A>      \
+                          : lenet_update_kernel<scalar_t, W, L, false, false, A>)
+#define CSED_UPDATE_PICK(W, L)                    \
+  if (p.world_bound == W && p.loopback == L) {    \
+    if (a.adam_v) CSED_UPDATE_PICK_A(W, L, true); \
+    else CSED_UPDATE_PICK_A(W, L, false);         \
+  }
   if (p.world_bound) {
     CSED_DISPATCH_UPDATE(a.mfma_dtype, {
       CSED_UPDATE_PICK(2, true);
@@ -2492,6 +2595,7 @@ hipError_t launch_lenet_update(const LenetUpdateArgs& a, float* loss_parts, int 
     CSED_DISPATCH_UPDATE(a.mfma_dtype, { CSED_UPDATE_PICK(0, false); });
   }
 #undef CSED_UPDATE_PICK
+#undef CSED_UPDATE_PICK_A
   if (!kern) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kern, dim3(p.blocks), dim3(UP_NT), 0, s, a, a.vslab, a.B, loss_parts, nparts, loss_acc, ticks,
                      p.fc_tpb, p.fc_sl, px);

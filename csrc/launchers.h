@@ -311,6 +311,20 @@ struct LenetUpdateArgs {
   // from the old ema[i] it loaded with p and m at kernel entry.  Null: off.  No plan dimension: form and
   // grid are those of the launch without it; the launcher picks the kernels' EMA instantiation from it.
   float* ema; float ema_decay;
+  // Adam / AdamW instead of SGD (optional; apply_sgd only, with step and ticket): adam_v is exp_avg_sq
+  // (fp32, one per parameter, 16-byte aligned; null: off) and exp_avg lives in ``momentum``.  With
+  // t = step[0] + 1, read by every block at its entry (so the launch takes tickets like a scheduled one):
+  //   g' = g + weight_decay * p              (adam_decoupled = 0: Adam)
+  //   p  = p * (1 - lr * weight_decay), g' = g  (adam_decoupled = 1: AdamW)
+  //   m += (1 - beta1) * (g' - m);  v = beta2 * v + (1 - beta2) * g'^2
+  //   p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + adam_eps)
+  // as torch.optim.Adam / AdamW (amsgrad = False, maximize = False), then the weight image and the moving
+  // average from the new p as under SGD.  mom, dampening and nesterov must be 0.  No plan dimension: the
+  // launcher picks the kernels' ADAM instantiation from adam_v != nullptr.
+  float* adam_v; float beta1, beta2, adam_eps; int adam_decoupled;
+  // log(beta1), log(beta2): filled by launch_lenet_update from the betas, in double, for the kernels'
+  // 1 - beta^t = -expm1f(t * log(beta)) (1 - powf(beta, t) cancels at small t); callers leave them alone
+  float adam_lb1, adam_lb2;
 };
 int64_t lenet_exch_words();
 int lenet_forced_fc_slices();  // CSED_FC_SLICES (0: automatic), read once per process
