@@ -85,7 +85,8 @@ void gather_normalize(const Tensor& src, const Tensor& idx, const optional<Tenso
 }
 
 // ------------------------------------------------------------- optimizer
-// A device-resident learning-rate schedule's table / position pair (optim/schedule.py), both or neither.
+// A device-resident learning-rate schedule's table / position pair (optim/schedule.py), both or neither: the
+// tensors.  (A table without entries is sgd_flat's own check below and, for lenet_update, the plan's.)
 void check_lr_schedule(const char* op, const Tensor& on, const optional<Tensor>& lr_table,
                        const optional<Tensor>& lr_pos) {
   TORCH_CHECK(lr_table.has_value() == lr_pos.has_value(), op, ": lr_table and lr_pos come together");
@@ -93,44 +94,18 @@ void check_lr_schedule(const char* op, const Tensor& on, const optional<Tensor>&
   dev(*lr_table, "lr_table"); dev(*lr_pos, "lr_pos");
   TORCH_CHECK(lr_table->device() == on.device() && lr_pos->device() == on.device(), op,
               ": lr_table / lr_pos must be on the parameters' device");
-  TORCH_CHECK(lr_table->scalar_type() == at::kFloat && lr_table->is_contiguous(), op, ": lr_table must be float32");
+  TORCH_CHECK(lr_table->scalar_type() == at::kFloat && lr_table->is_contiguous() && lr_table->numel() <= INT32_MAX,
+              op, ": lr_table must be float32");
   TORCH_CHECK(lr_pos->scalar_type() == at::kLong && lr_pos->numel() == 1, op, ": lr_pos must be int64[1]");
-  TORCH_CHECK(lr_table->numel() >= 1 && lr_table->numel() <= INT32_MAX, op, ": lr_table needs at least one entry");
 }
 
-// The parameters' exponential moving average (optional): one fp32 value per parameter on their device,
-// updated by the launch that applies SGD with a decay in [0, 1).
-void check_ema(const char* op, const Tensor& params, const optional<Tensor>& ema, double ema_decay, bool apply_sgd) {
-  if (!ema.has_value()) return;
-  TORCH_CHECK(apply_sgd, op, ": ema comes only with apply_sgd (a reduce-only launch changes no parameter)");
-  TORCH_CHECK(ema->is_cuda() && ema->device() == params.device(), op, ": ema must be on the parameters' device");
-  TORCH_CHECK(ema->scalar_type() == at::kFloat && ema->is_contiguous(), op, ": ema must be contiguous float32");
-  TORCH_CHECK(ema->numel() == params.numel(), op, ": ema must hold one value per parameter (", params.numel(),
-              "), got ", ema->numel());
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(ema->data_ptr()) & 15) == 0, op, ": ema must be 16-byte aligned");
-  TORCH_CHECK(ema_decay >= 0.0 && ema_decay < 1.0, op, ": ema_decay must be in [0, 1), got ", ema_decay);
-}
-
-// Adam / AdamW in place of SGD (csed::lenet_update_adam): exp_avg_sq, one fp32 value per parameter on their
-// device, and the rule's constants.  exp_avg lives in the momentum buffer, so SGD's own arguments must be zero.
-struct AdamOpt {
-  const Tensor& v; double beta1, beta2, eps; bool decoupled;
-};
-void check_adam(const char* op, const Tensor& params, const AdamOpt& ad, bool apply_sgd, double mom, double dampening,
-                bool nesterov) {
-  TORCH_CHECK(apply_sgd, op, ": Adam comes only with apply_sgd (a reduce-only launch changes no parameter)");
-  TORCH_CHECK(ad.v.is_cuda() && ad.v.device() == params.device(), op, ": adam_v must be on the parameters' device");
-  TORCH_CHECK(ad.v.scalar_type() == at::kFloat && ad.v.is_contiguous(), op, ": adam_v must be contiguous float32");
-  TORCH_CHECK(ad.v.numel() == params.numel(), op, ": adam_v must hold one value per parameter (", params.numel(),
-              "), got ", ad.v.numel());
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(ad.v.data_ptr()) & 15) == 0, op, ": adam_v must be 16-byte aligned");
-  TORCH_CHECK(ad.beta1 >= 0.0 && ad.beta1 < 1.0, op, ": beta1 must be in [0, 1), got ", ad.beta1);
-  TORCH_CHECK(ad.beta2 >= 0.0 && ad.beta2 < 1.0, op, ": beta2 must be in [0, 1), got ", ad.beta2);
-  TORCH_CHECK((float)ad.eps > 0.f, op, ": eps must be positive (in float32), got ", ad.eps);
-  TORCH_CHECK((float)ad.beta1 < 1.f && (float)ad.beta2 < 1.f, op, ": the betas must be below 1 in float32");
-  TORCH_CHECK(mom == 0.0 && dampening == 0.0 && !nesterov, op,
-              ": mom, dampening and nesterov are SGD's and must be 0 under Adam (got mom ", mom, ", dampening ",
-              dampening, ", nesterov ", nesterov, ")");
+// A per-parameter state buffer of lenet_update (ema; adam_v, Adam's exp_avg_sq): one fp32 value per parameter on
+// their device.  Its alignment and the constants that go with it: csed::lenet_update_rule.
+void check_param_buffer(const char* op, const char* name, const Tensor& params, const Tensor& t) {
+  TORCH_CHECK(t.is_cuda() && t.device() == params.device(), op, ": ", name, " must be on the parameters' device");
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous(), op, ": ", name, " must be contiguous float32");
+  TORCH_CHECK(t.numel() == params.numel(), op, ": ", name, " must hold one value per parameter (", params.numel(),
+              "), got ", t.numel());
 }
 
 void sgd_flat(Tensor& p, const Tensor& g, Tensor& buf, double lr, double momentum, double dampening,
@@ -138,6 +113,7 @@ void sgd_flat(Tensor& p, const Tensor& g, Tensor& buf, double lr, double momentu
               const optional<Tensor>& lr_table, const optional<Tensor>& lr_pos) {
   dev(p, "p"); dev(g, "g"); dev(buf, "buf");
   check_lr_schedule("sgd_flat", p, lr_table, lr_pos);
+  TORCH_CHECK(!lr_table.has_value() || lr_table->numel() >= 1, "sgd_flat: lr_table needs at least one entry");
   TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat && buf.scalar_type() == at::kFloat);
   TORCH_CHECK(p.numel() == g.numel() && p.numel() == buf.numel());
   TORCH_CHECK(step.scalar_type() == at::kLong && ticket.scalar_type() == at::kInt);
@@ -868,22 +844,51 @@ void lenet_stage(const Tensor& images, const Tensor& labels, const Tensor& perm,
                                      cursor.data_ptr<int64_t>(), cur_stream(images)));
 }
 
-csed::LenetUpdateArgs update_args(const Tensor& slab, int64_t grid, const Tensor& vslab, int64_t B,
-                                  const optional<Tensor>& grad_in, const optional<Tensor>& grad_out, Tensor& params,
-                                  Tensor& momentum, Tensor& wimg, double lr, double mom, double dampening,
-                                  double weight_decay, bool nesterov, Tensor& step, Tensor& ticket,
-                                  const optional<Tensor>& cursor, const optional<Tensor>& rng_offset, bool apply_sgd,
-                                  const optional<Tensor>& loss_parts, const optional<Tensor>& loss_acc,
-                                  int64_t mfma_dtype, const optional<Tensor>& dbg, int64_t exch_id,
-                                  double exch_timeout_s, double grad_post, const optional<Tensor>& fc_part,
-                                  const optional<Tensor>& lr_table, const optional<Tensor>& lr_pos,
-                                  const optional<Tensor>& ema, double ema_decay, const AdamOpt* adam = nullptr) {
+// A checked lenet_update launch: the kernel's argument block, the exchange buffer's device view (a.exch_id >= 0,
+// resolved once here so that a launch does no registry lookup) and what the launcher takes apart from the block.
+struct UpdateLaunch {
+  csed::LenetUpdateArgs a{};
+  csed::comm::IpcPeers px{};
+  float *loss_parts = nullptr, *loss_acc = nullptr;
+  int nparts = 0;
+  c10::DeviceIndex device = -1;  // the parameters'
+
+  void run(hipStream_t s) const { CHECK_HIP(csed::launch_lenet_update(a, loss_parts, nparts, loss_acc, s, &px)); }
+};
+
+// Adam / AdamW in place of SGD: exp_avg_sq and the rule's constants (exp_avg lives in the momentum buffer).
+void set_adam(const char* op, const Tensor& params, csed::LenetUpdateArgs& a, const Tensor& adam_v, double beta1,
+              double beta2, double eps, bool decoupled) {
+  check_param_buffer(op, "adam_v", params, adam_v);
+  a.adam_v = adam_v.data_ptr<float>(); a.beta1 = (float)beta1; a.beta2 = (float)beta2;
+  a.adam_eps = (float)eps; a.adam_decoupled = decoupled ? 1 : 0;
+}
+
+// The launch that csed::lenet_update's arguments describe (Adam: none), or csed::lenet_update_adam's (Adam: adam_v,
+// beta1, beta2, eps, decoupled behind them): the tensor checks, then the plan (kernels/lenet_plan.h: which form,
+// instantiation and grid the launch gets) and the optimizer options' rule, each raised as "<op>: <sentence>".
+// The only place that spells the argument list: the ops and LenetStepper's setters read it off this signature.
+template <typename... Adam>
+UpdateLaunch update_launch(const Tensor& slab, int64_t grid, const Tensor& vslab, int64_t B,
+                           const optional<Tensor>& grad_in, const optional<Tensor>& grad_out, const Tensor& params,
+                           const Tensor& momentum, const Tensor& wimg, double lr, double mom, double dampening,
+                           double weight_decay, bool nesterov, const Tensor& step, const Tensor& ticket,
+                           const optional<Tensor>& cursor, const optional<Tensor>& rng_offset, bool apply_sgd,
+                           const optional<Tensor>& loss_parts, int64_t nparts, const optional<Tensor>& loss_acc,
+                           int64_t mfma_dtype, const optional<Tensor>& dbg, int64_t exch_id, double exch_timeout_s,
+                           double grad_post, const optional<Tensor>& fc_part, const optional<Tensor>& lr_table,
+                           const optional<Tensor>& lr_pos, const optional<Tensor>& ema, double ema_decay,
+                           Adam... adam) {
+  constexpr const char* op = sizeof...(Adam) ? "lenet_update_adam" : "lenet_update";
   dev(slab, "slab"); dev(params, "params"); dev(momentum, "momentum"); dev(wimg, "wimg");
   TORCH_CHECK(params.numel() == csed::lenet_param_count() && momentum.numel() == params.numel(),
               "lenet_update: params / momentum must hold the 21840 flat LeNet parameters");
   TORCH_CHECK(apply_sgd || grad_out.has_value(), "lenet_update: reduce-only mode needs grad_out");
   TORCH_CHECK(loss_parts.has_value() == loss_acc.has_value());
-  csed::LenetUpdateArgs a{};
+  UpdateLaunch u;
+  u.loss_parts = optpt<float>(loss_parts); u.nparts = (int)nparts; u.loss_acc = optpt<float>(loss_acc);
+  u.device = params.device().index();
+  csed::LenetUpdateArgs& a = u.a;
   a.slab = slab.data_ptr<float>(); a.grid = (int)grid;
   a.vslab = vslab.data_ptr<float>(); a.B = (int)B;
   TORCH_CHECK(vslab.scalar_type() == at::kFloat && vslab.numel() * 4 >= vec_bytes(B, mfma_dtype),
@@ -906,79 +911,27 @@ csed::LenetUpdateArgs update_args(const Tensor& slab, int64_t grid, const Tensor
     a.fc_part = fc_part->data_ptr<float>();
     a.fc_part_n = fc_part->numel();
   }
-  // exch_id >= 0: csrc/comm buffer of the fused gradient exchange (resolved and checked by update_plan below)
+  // exch_id >= 0: csrc/comm buffer of the fused gradient exchange
   a.exch_id = (int)exch_id; a.exch_timeout_s = exch_timeout_s;
   // device-resident learning-rate schedule: the kernel that applies SGD picks its step's rate
-  check_lr_schedule("lenet_update", params, lr_table, lr_pos);
+  check_lr_schedule(op, params, lr_table, lr_pos);
   if (lr_table.has_value()) {
     a.lr_table = lr_table->data_ptr<float>(); a.lr_len = (int)lr_table->numel();
     a.lr_pos = lr_pos->data_ptr<int64_t>();
   }
   // the parameters' moving average, updated by the launch that applies SGD
-  check_ema("lenet_update", params, ema, ema_decay, apply_sgd);
   if (ema.has_value()) {
+    check_param_buffer(op, "ema", params, *ema);
     a.ema = ema->data_ptr<float>(); a.ema_decay = (float)ema_decay;
   }
-  // Adam / AdamW in place of SGD (lenet_update_adam, set_update_adam)
-  if (adam) {
-    check_adam("lenet_update_adam", params, *adam, apply_sgd, mom, dampening, nesterov);
-    a.adam_v = adam->v.data_ptr<float>(); a.beta1 = (float)adam->beta1; a.beta2 = (float)adam->beta2;
-    a.adam_eps = (float)adam->eps; a.adam_decoupled = adam->decoupled ? 1 : 0;
-  }
-  return a;
-}
-
-// The exchange buffer's device view (a.exch_id >= 0) and the launch's plan (kernels/lenet_plan.h): which
-// form, instantiation and grid it gets, or the rule the argument block breaks.
-csed::LenetUpdatePlan update_plan(const csed::LenetUpdateArgs& a, csed::comm::IpcPeers* px) {
-  *px = {};
-  if (a.exch_id >= 0) CHECK_HIP(csed::comm::ipc_peers(a.exch_id, px));
-  const csed::LenetUpdatePlan plan = csed::lenet_update_plan(a, *px);
-  TORCH_CHECK(!plan.error, "lenet_update: ", plan.error);
-  return plan;
-}
-
-void lenet_update(const Tensor& slab, int64_t grid, const Tensor& vslab, int64_t B, const optional<Tensor>& grad_in, const optional<Tensor>& grad_out,
-                  Tensor& params, Tensor& momentum, Tensor& wimg, double lr, double mom, double dampening,
-                  double weight_decay, bool nesterov, Tensor& step, Tensor& ticket, const optional<Tensor>& cursor,
-                  const optional<Tensor>& rng_offset, bool apply_sgd, const optional<Tensor>& loss_parts,
-                  int64_t nparts, const optional<Tensor>& loss_acc, int64_t mfma_dtype, const optional<Tensor>& dbg,
-                  int64_t exch_id, double exch_timeout_s, double grad_post, const optional<Tensor>& fc_part,
-                  const optional<Tensor>& lr_table, const optional<Tensor>& lr_pos, const optional<Tensor>& ema,
-                  double ema_decay) {
-  const c10::DeviceGuard gd(params.device());
-  const csed::LenetUpdateArgs a =
-      update_args(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
-                  nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts, loss_acc, mfma_dtype, dbg,
-                  exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos, ema, ema_decay);
-  csed::comm::IpcPeers px;
-  update_plan(a, &px);
-  CHECK_HIP(csed::launch_lenet_update(a, optpt<float>(loss_parts), (int)nparts, optpt<float>(loss_acc),
-                                      cur_stream(params), &px));
-}
-
-// lenet_update with Adam / AdamW in place of SGD: its arguments in order, then exp_avg_sq and the rule's
-// constants; exp_avg is ``momentum``.  The same builder, plan and launcher.
-void lenet_update_adam(const Tensor& slab, int64_t grid, const Tensor& vslab, int64_t B,
-                       const optional<Tensor>& grad_in, const optional<Tensor>& grad_out, Tensor& params,
-                       Tensor& momentum, Tensor& wimg, double lr, double mom, double dampening, double weight_decay,
-                       bool nesterov, Tensor& step, Tensor& ticket, const optional<Tensor>& cursor,
-                       const optional<Tensor>& rng_offset, bool apply_sgd, const optional<Tensor>& loss_parts,
-                       int64_t nparts, const optional<Tensor>& loss_acc, int64_t mfma_dtype,
-                       const optional<Tensor>& dbg, int64_t exch_id, double exch_timeout_s, double grad_post,
-                       const optional<Tensor>& fc_part, const optional<Tensor>& lr_table,
-                       const optional<Tensor>& lr_pos, const optional<Tensor>& ema, double ema_decay, Tensor& adam_v,
-                       double beta1, double beta2, double eps, bool decoupled) {
-  const c10::DeviceGuard gd(params.device());
-  const AdamOpt ad{adam_v, beta1, beta2, eps, decoupled};
-  const csed::LenetUpdateArgs a =
-      update_args(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
-                  nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts, loss_acc, mfma_dtype, dbg,
-                  exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos, ema, ema_decay, &ad);
-  csed::comm::IpcPeers px;
-  update_plan(a, &px);
-  CHECK_HIP(csed::launch_lenet_update(a, optpt<float>(loss_parts), (int)nparts, optpt<float>(loss_acc),
-                                      cur_stream(params), &px));
+  if constexpr (sizeof...(Adam) > 0) set_adam(op, params, a, adam...);
+  if (a.exch_id >= 0) CHECK_HIP(csed::comm::ipc_peers(a.exch_id, &u.px));
+  const csed::LenetUpdatePlan plan = csed::lenet_update_plan(a, u.px);
+  TORCH_CHECK(!plan.error, op, ": ", plan.error);
+  const char* rule = csed::lenet_update_rule(a);
+  TORCH_CHECK(!rule, op, ": ", rule, " (got ema_decay ", a.ema_decay, ", beta1 ", a.beta1, ", beta2 ", a.beta2, ", eps ",
+              a.adam_eps, ", mom ", a.mom, ", dampening ", a.dampening, ", nesterov ", a.nesterov, ")");
+  return u;
 }
 
 // kernels/lenet_plan.h lenet_update_plan for Python (engine/fused.py LenetUpdatePlan; integers only, so no GPU):
@@ -1100,10 +1053,7 @@ struct HipGraph : torch::CustomClassHolder {
 // window) pays no graph-launch setup and no Python per launch; long runs replay graphs (engine/fused.py:step_plan).
 struct LenetStepper : torch::CustomClassHolder {
   csed::LenetTrainArgs ta{};
-  csed::LenetUpdateArgs ua{};
-  float *loss_parts = nullptr, *loss_acc = nullptr;  // (the update launcher takes these apart from ua)
-  int64_t nparts = 0;
-  csed::comm::IpcPeers px{};  // the exchange buffer's device view (ua.exch_id >= 0)
+  UpdateLaunch up{};
   int device = -1;
   std::vector<optional<Tensor>> keep_t, keep_u;  // every tensor the argument blocks point into stays alive
 
@@ -1118,73 +1068,47 @@ struct LenetStepper : torch::CustomClassHolder {
     keep_t = {images, labels, perm, cursor, wimg, params, slab, vslab, loss_parts_t, rng_offset, dbg, xstage, lstage};
   }
 
-  void set_update(Tensor slab, int64_t grid, Tensor vslab, int64_t B, optional<Tensor> grad_in,
-                  optional<Tensor> grad_out, Tensor params, Tensor momentum, Tensor wimg, double lr, double mom,
-                  double dampening, double weight_decay, bool nesterov, Tensor step, Tensor ticket,
-                  optional<Tensor> cursor, optional<Tensor> rng_offset, bool apply_sgd, optional<Tensor> loss_parts_t,
-                  int64_t nparts_, optional<Tensor> loss_acc_t, int64_t mfma_dtype, optional<Tensor> dbg,
-                  int64_t exch_id, double exch_timeout_s, double grad_post, optional<Tensor> fc_part,
-                  optional<Tensor> lr_table, optional<Tensor> lr_pos, optional<Tensor> ema, double ema_decay) {
-    set_update_impl(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
-                    nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts_t, nparts_, loss_acc_t,
-                    mfma_dtype, dbg, exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos, ema, ema_decay,
-                    nullptr);
-  }
-
-  // set_update with Adam / AdamW in place of SGD (csed::lenet_update_adam's argument list); run() replays
-  // whichever update was set last.
-  void set_update_adam(Tensor slab, int64_t grid, Tensor vslab, int64_t B, optional<Tensor> grad_in,
-                       optional<Tensor> grad_out, Tensor params, Tensor momentum, Tensor wimg, double lr, double mom,
-                       double dampening, double weight_decay, bool nesterov, Tensor step, Tensor ticket,
-                       optional<Tensor> cursor, optional<Tensor> rng_offset, bool apply_sgd,
-                       optional<Tensor> loss_parts_t, int64_t nparts_, optional<Tensor> loss_acc_t, int64_t mfma_dtype,
-                       optional<Tensor> dbg, int64_t exch_id, double exch_timeout_s, double grad_post,
-                       optional<Tensor> fc_part, optional<Tensor> lr_table, optional<Tensor> lr_pos,
-                       optional<Tensor> ema, double ema_decay, Tensor adam_v, double beta1, double beta2, double eps,
-                       bool decoupled) {
-    const AdamOpt ad{adam_v, beta1, beta2, eps, decoupled};
-    set_update_impl(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
-                    nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts_t, nparts_, loss_acc_t,
-                    mfma_dtype, dbg, exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos, ema, ema_decay,
-                    &ad);
-  }
-
-  void set_update_impl(Tensor& slab, int64_t grid, Tensor& vslab, int64_t B, optional<Tensor>& grad_in,
-                       optional<Tensor>& grad_out, Tensor& params, Tensor& momentum, Tensor& wimg, double lr,
-                       double mom, double dampening, double weight_decay, bool nesterov, Tensor& step, Tensor& ticket,
-                       optional<Tensor>& cursor, optional<Tensor>& rng_offset, bool apply_sgd,
-                       optional<Tensor>& loss_parts_t, int64_t nparts_, optional<Tensor>& loss_acc_t,
-                       int64_t mfma_dtype, optional<Tensor>& dbg, int64_t exch_id, double exch_timeout_s,
-                       double grad_post, optional<Tensor>& fc_part, optional<Tensor>& lr_table,
-                       optional<Tensor>& lr_pos, optional<Tensor>& ema, double ema_decay, const AdamOpt* adam) {
-    TORCH_CHECK(apply_sgd && !grad_in && !grad_out && cursor, "LenetStepper: set_update takes a full step at a cursor");
-    const csed::LenetUpdateArgs a =
-        update_args(slab, grid, vslab, B, grad_in, grad_out, params, momentum, wimg, lr, mom, dampening, weight_decay,
-                    nesterov, step, ticket, cursor, rng_offset, apply_sgd, loss_parts_t, loss_acc_t, mfma_dtype, dbg,
-                    exch_id, exch_timeout_s, grad_post, fc_part, lr_table, lr_pos, ema, ema_decay, adam);
-    csed::comm::IpcPeers peers;
-    update_plan(a, &peers);  // the exchange's view and the plan's error once, here: a bad block never reaches run()
-    ua = a;
-    px = peers;
-    loss_parts = optpt<float>(loss_parts_t);
-    loss_acc = optpt<float>(loss_acc_t);
-    nparts = nparts_;
-    keep_u = {slab,   vslab,      params,       momentum,   wimg, step,   ticket,
-              cursor, rng_offset, loss_parts_t, loss_acc_t, dbg,  fc_part, lr_table, lr_pos, ema,
-              adam ? optional<Tensor>(adam->v) : optional<Tensor>()};
+  // set_update / set_update_adam (UpdateEntry::set below): a checked launch, so a bad block never reaches run(),
+  // which replays whichever update was set last.
+  void set_update(const UpdateLaunch& u, std::vector<optional<Tensor>> keep) {
+    TORCH_CHECK(u.a.apply_sgd && !u.a.grad_in && !u.a.grad_out && u.a.cursor,
+                "LenetStepper: set_update takes a full step at a cursor");
+    up = u;
+    keep_u = std::move(keep);
   }
 
   void run(int64_t k) {
-    TORCH_CHECK(device >= 0 && ua.params, "LenetStepper: set_train and set_update first");
-    TORCH_CHECK(ta.cursor && ua.cursor == ta.cursor, "LenetStepper: full steps advance one device cursor");
+    TORCH_CHECK(device >= 0 && up.a.params, "LenetStepper: set_train and set_update first");
+    TORCH_CHECK(ta.cursor && up.a.cursor == ta.cursor, "LenetStepper: full steps advance one device cursor");
     const c10::DeviceGuard gd(c10::Device(c10::DeviceType::CUDA, (c10::DeviceIndex)device));
     const hipStream_t s = c10::hip::getCurrentHIPStream(device).stream();
     for (int64_t i = 0; i < k; ++i) {
       CHECK_HIP(csed::launch_lenet_train(ta, s));
-      CHECK_HIP(csed::launch_lenet_update(ua, loss_parts, (int)nparts, loss_acc, s, ua.exch_id >= 0 ? &px : nullptr));
+      up.run(s);
     }
   }
 };
+
+// what an argument keeps alive: a tensor itself, nothing for a scalar
+optional<Tensor> held(const Tensor& t) { return t; }
+optional<Tensor> held(const optional<Tensor>& t) { return t; }
+template <typename T> optional<Tensor> held(T) { return {}; }
+
+// csed::lenet_update / lenet_update_adam and LenetStepper.set_update / set_update_adam over update_launch<...>:
+// each takes exactly the builder's arguments A, so a change of the list is made there and in the schema strings.
+template <auto build, typename = decltype(build)>
+struct UpdateEntry;
+template <auto build, typename... A>
+struct UpdateEntry<build, UpdateLaunch (*)(A...)> {
+  static void op(A... a) {
+    const UpdateLaunch u = build(a...);
+    const c10::DeviceGuard gd(c10::Device(c10::DeviceType::CUDA, u.device));
+    u.run(c10::hip::getCurrentHIPStream(u.device).stream());
+  }
+  static void set(const c10::intrusive_ptr<LenetStepper>& self, A... a) { self->set_update(build(a...), {held(a)...}); }
+};
+using UpdateSgd = UpdateEntry<&update_launch<>>;
+using UpdateAdam = UpdateEntry<&update_launch<const Tensor&, double, double, double, bool>>;
 
 }  // namespace
 
@@ -1200,8 +1124,8 @@ TORCH_LIBRARY(csed, m) {
   m.class_<LenetStepper>("LenetStepper")
       .def(torch::init<>())
       .def("set_train", &LenetStepper::set_train)
-      .def("set_update", &LenetStepper::set_update)
-      .def("set_update_adam", &LenetStepper::set_update_adam)
+      .def("set_update", &UpdateSgd::set)
+      .def("set_update_adam", &UpdateAdam::set)
       .def("run", &LenetStepper::run);
   m.def("lenet_layout() -> int[]", &lenet_layout);
   m.def("lenet_plan(int B, int grid, int mfma_dtype, int kernel, bool staged, bool stage_next, bool cursor, bool train) "
@@ -1321,8 +1245,8 @@ TORCH_LIBRARY_IMPL(csed, CUDA, m) {
   m.impl("lsm_nll_bwd", &lsm_nll_bwd);
   m.impl("lenet_pack", &lenet_pack);
   m.impl("lenet_train", &lenet_train);
-  m.impl("lenet_update", &lenet_update);
-  m.impl("lenet_update_adam", &lenet_update_adam);
+  m.impl("lenet_update", &UpdateSgd::op);
+  m.impl("lenet_update_adam", &UpdateAdam::op);
   m.impl("lenet_stage", &lenet_stage);
   m.impl("lenet_eval", &lenet_eval);
 }

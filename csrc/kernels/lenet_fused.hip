@@ -2517,24 +2517,35 @@ int lenet_forced_fc_slices() {
   return forced;
 }
 
+// The kernels' (SCHED, EMA, ADAM) instantiations, indexed by sched + 2 * ema + 4 * adam.  EMA and ADAM are
+// template flags chosen from a.ema / a.adam_v != nullptr, not run-time tests and no plan dimension (form, grid
+// and trailing arguments are those of the launch without them): measured (profiles/ema.md), a run-time test
+// on a.ema cost the EMA-off step 0.58 us of 13.26, far outside the parent's own spread.
+using SgdKernel = void (*)(LenetUpdateArgs);
+template <typename T>
+constexpr SgdKernel sgd_kernels[8] = {
+    lenet_sgd_kernel<T, false, false, false>, lenet_sgd_kernel<T, true, false, false>,
+    lenet_sgd_kernel<T, false, true, false>,  lenet_sgd_kernel<T, true, true, false>,
+    lenet_sgd_kernel<T, false, false, true>,  lenet_sgd_kernel<T, true, false, true>,
+    lenet_sgd_kernel<T, false, true, true>,   lenet_sgd_kernel<T, true, true, true>};
+using UpdateKernel = void (*)(LenetUpdateArgs, const float*, int, float*, int, float*, uint64_t, int, int,
+                              comm::IpcPeers);
+template <typename T, int XW, bool LBC>
+constexpr UpdateKernel update_kernels[8] = {
+    lenet_update_kernel<T, XW, LBC, false, false, false>, lenet_update_kernel<T, XW, LBC, true, false, false>,
+    lenet_update_kernel<T, XW, LBC, false, true, false>,  lenet_update_kernel<T, XW, LBC, true, true, false>,
+    lenet_update_kernel<T, XW, LBC, false, false, true>,  lenet_update_kernel<T, XW, LBC, true, false, true>,
+    lenet_update_kernel<T, XW, LBC, false, true, true>,   lenet_update_kernel<T, XW, LBC, true, true, true>};
+
 // Runs what lenet_update_plan (kernels/lenet_plan.h) decides: lenet_sgd_kernel on grad_in, or
 // lenet_update_kernel in the plan's (XW, LBC, SCHED) instantiation, on its grid, with its trailing arguments.
 hipError_t launch_lenet_update(const LenetUpdateArgs& a_in, float* loss_parts, int nparts, float* loss_acc,
                                hipStream_t s, const comm::IpcPeers* px_cached) {
-  // Adam / AdamW is no plan dimension either: a template flag chosen here from a.adam_v != nullptr, like the
-  // moving average below and for its reason.  It replaces SGD's rule, so it comes with apply_sgd, reads
-  // step[0] in every block (hence the ticket) and leaves SGD's own arguments no meaning: they must be zero.
-  // The kernels get log(beta) from here, in double (adam_step).
+  if (lenet_update_rule(a_in)) return hipErrorInvalidValue;  // the moving average's and Adam's own rules
+  // Adam's kernels get log(beta) from here, in double (adam_step).
   LenetUpdateArgs a = a_in;
-  a.adam_lb1 = a.adam_lb2 = 0.f;
-  if (a.adam_v) {
-    const bool betas = a.beta1 >= 0.f && a.beta1 < 1.f && a.beta2 >= 0.f && a.beta2 < 1.f;
-    if (!a.apply_sgd || !a.step || !a.ticket || ((uintptr_t)a.adam_v & 15) || !betas || !(a.adam_eps > 0.f) ||
-        a.mom != 0.f || a.dampening != 0.f || a.nesterov != 0)
-      return hipErrorInvalidValue;
-    a.adam_lb1 = (float)std::log((double)a.beta1);
-    a.adam_lb2 = (float)std::log((double)a.beta2);
-  }
+  a.adam_lb1 = a.adam_v ? (float)std::log((double)a.beta1) : 0.f;
+  a.adam_lb2 = a.adam_v ? (float)std::log((double)a.beta2) : 0.f;
   static_assert(NB_UPDATE <= comm::kIpcMaxBlocks, "one exchange counter per update workgroup");
   comm::IpcPeers px{};
   if (a.exch_id >= 0) {
@@ -2547,55 +2558,27 @@ hipError_t launch_lenet_update(const LenetUpdateArgs& a_in, float* loss_parts, i
   }
   const LenetUpdatePlan p = lenet_update_plan(a, px);
   if (p.error) return hipErrorInvalidValue;
-  // The moving average is no plan dimension: form, grid and trailing arguments are those of the launch
-  // without one.  The kernels take it as a template flag chosen here from a.ema != nullptr, not as a
-  // run-time test: measured (profiles/ema.md), the run-time test on a.ema cost the EMA-off step 0.58 us
-  // of 13.26, far outside the parent's own spread.  It goes with SGD alone, and its fc1 rows are read and
-  // written as float4 like the parameters'.
-  if (a.ema && (!a.apply_sgd || !(a.ema_decay >= 0.f && a.ema_decay < 1.f) || ((uintptr_t)a.ema & 15)))
-    return hipErrorInvalidValue;
+  const int flags = (p.sched ? 1 : 0) + (a.ema ? 2 : 0) + (a.adam_v ? 4 : 0);
   if (p.form == kUpdateSgd) {
-#define CSED_SGD_PICK(A)                                                                                             \
-  kern = a.ema ? (p.sched ? lenet_sgd_kernel<scalar_t, true, true, A> : lenet_sgd_kernel<scalar_t, false, true, A>) \
-               : (p.sched ? lenet_sgd_kernel<scalar_t, true, false, A> : lenet_sgd_kernel<scalar_t, false, false, A>)
-    CSED_DISPATCH_UPDATE(a.mfma_dtype, {
-      void (*kern)(LenetUpdateArgs) = nullptr;
-      if (a.adam_v) CSED_SGD_PICK(true);
-      else CSED_SGD_PICK(false);
-      hipLaunchKernelGGL(kern, dim3(p.blocks), dim3(256), 0, s, a);
-    });
-#undef CSED_SGD_PICK
+    CSED_DISPATCH_UPDATE(a.mfma_dtype,
+                         { hipLaunchKernelGGL(sgd_kernels<scalar_t>[flags], dim3(p.blocks), dim3(256), 0, s, a); });
     return hipGetLastError();
   }
   const uint64_t ticks = p.form == kUpdateExchange ? (uint64_t)(a.exch_timeout_s * 1e8) : 0;  // s_memrealtime: 100 MHz
-  // The (XW, LBC, SCHED) instantiations that occur: the exchange's world bound 2 / 4 / 8, looped back (its
-  // invariant check) or not, and XW = 0 without one; each with and without the schedule, the moving average
-  // and Adam.
-  void (*kern)(LenetUpdateArgs, const float*, int, float*, int, float*, uint64_t, int, int, comm::IpcPeers) = nullptr;
-#define CSED_UPDATE_PICK_A(W, L, A)                                                  \
-  kern = a.ema ? (p.sched ? lenet_update_kernel<scalar_t, W, L, true, true, A>       \
-                          : lenet_update_kernel<scalar_t, W, L, false, true, A>)     \
-               : (p.sched ? lenet_update_kernel<scalar_t, W, L, true, false, A>      \
-                          : lenet_update_kernel<scalar_t, W, L, false, false, A>)
-#define CSED_UPDATE_PICK(W, L)                    \
-  if (p.world_bound == W && p.loopback == L) {    \
-    if (a.adam_v) CSED_UPDATE_PICK_A(W, L, true); \
-    else CSED_UPDATE_PICK_A(W, L, false);         \
-  }
-  if (p.world_bound) {
-    CSED_DISPATCH_UPDATE(a.mfma_dtype, {
-      CSED_UPDATE_PICK(2, true);
-      CSED_UPDATE_PICK(4, true);
-      CSED_UPDATE_PICK(8, true);
-      CSED_UPDATE_PICK(2, false);
-      CSED_UPDATE_PICK(4, false);
-      CSED_UPDATE_PICK(8, false);
-    });
-  } else {
-    CSED_DISPATCH_UPDATE(a.mfma_dtype, { CSED_UPDATE_PICK(0, false); });
-  }
-#undef CSED_UPDATE_PICK
-#undef CSED_UPDATE_PICK_A
+  // The (XW, LBC) instantiations that occur: the exchange's world bound 2 / 4 / 8, looped back (its invariant
+  // check) or not, and XW = 0 without one.
+  UpdateKernel kern = nullptr;
+  CSED_DISPATCH_UPDATE(a.mfma_dtype, {
+    switch (2 * p.world_bound + (p.loopback ? 1 : 0)) {
+      case 0: kern = update_kernels<scalar_t, 0, false>[flags]; break;
+      case 4: kern = update_kernels<scalar_t, 2, false>[flags]; break;
+      case 5: kern = update_kernels<scalar_t, 2, true>[flags]; break;
+      case 8: kern = update_kernels<scalar_t, 4, false>[flags]; break;
+      case 9: kern = update_kernels<scalar_t, 4, true>[flags]; break;
+      case 16: kern = update_kernels<scalar_t, 8, false>[flags]; break;
+      case 17: kern = update_kernels<scalar_t, 8, true>[flags]; break;
+    }
+  });
   if (!kern) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kern, dim3(p.blocks), dim3(UP_NT), 0, s, a, a.vslab, a.B, loss_parts, nparts, loss_acc, ticks,
                      p.fc_tpb, p.fc_sl, px);

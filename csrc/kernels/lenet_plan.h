@@ -3,7 +3,8 @@
 // gets: decided here and nowhere else.  The launchers (lenet_fused.hip, lenet_tile.hip,
 // lenet_fused_f32.hip) dispatch on lenet_plan() / lenet_update_plan(), the ops (bindings.cpp) report
 // their message, and Python asks through csed::lenet_plan / csed::lenet_geometry /
-// csed::lenet_update_plan (engine/fused.py).  A new kernel variant is added here.  Plain integer logic:
+// csed::lenet_update_plan (engine/fused.py).  lenet_update_rule() holds the rules of lenet_update's optimizer
+// options (EMA, Adam / AdamW), for the launcher and the ops alike.  A new kernel variant is added here.  Plain scalar logic:
 // no HIP call, no environment, no allocation (tests/native/plan_check.cpp runs it on the host).
 #pragma once
 #include <stdint.h>
@@ -213,6 +214,30 @@ inline LenetUpdatePlan lenet_update_plan(int B, bool apply_sgd, bool grad_in, bo
   p.fc_blocks = p.fc_tpb ? FC_TILES * p.slices : fc_blocks(B);
   p.blocks = p.fc_blocks + NB_CONV;
   return p;
+}
+
+// The launch's optimizer options, which are no plan dimension (the kernels' EMA / ADAM template flags): the
+// rule they break, or null.  The launcher and the ops (launchers.h lenet_update_rule(LenetUpdateArgs)) both
+// ask here, with the float32 values the kernel will see.  ema / adam_v: the buffers' addresses, 0 for none.
+inline const char* lenet_update_rule(bool apply_sgd, bool step, bool ticket, float mom, float dampening, bool nesterov,
+                                     uintptr_t ema, float ema_decay, uintptr_t adam_v, float beta1, float beta2,
+                                     float eps) {
+  const auto unit = [](float x) { return x >= 0.f && x < 1.f; };  // (false for a NaN)
+  if (ema) {
+    if (!apply_sgd) return "ema comes only with apply_sgd (a reduce-only launch changes no parameter)";
+    if (!unit(ema_decay)) return "ema_decay must be in [0, 1) in float32";
+    if (ema & 15) return "ema must be 16-byte aligned";
+  }
+  if (!adam_v) return nullptr;
+  return !apply_sgd         ? "Adam comes only with apply_sgd (a reduce-only launch changes no parameter)"
+         : !step || !ticket ? "Adam reads the step number in every block: it needs step and ticket"
+         : adam_v & 15      ? "adam_v must be 16-byte aligned"
+         : !unit(beta1)     ? "beta1 must be in [0, 1) in float32"
+         : !unit(beta2)     ? "beta2 must be in [0, 1) in float32"
+         : !(eps > 0.f)     ? "eps must be positive in float32"
+         : mom != 0.f || dampening != 0.f || nesterov
+             ? "mom, dampening and nesterov are SGD's and must be 0 under Adam"
+             : nullptr;
 }
 
 // The engine allocates the split-K scratch from this per-rank batch on: past one automatic slice's worth

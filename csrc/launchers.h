@@ -336,7 +336,13 @@ inline LenetUpdatePlan lenet_update_plan(const LenetUpdateArgs& a, const comm::I
                            a.exch_timeout_s > 0.0, a.lr_table != nullptr, a.lr_pos != nullptr, a.ticket != nullptr,
                            a.lr_len, a.fc_part ? a.fc_part_n : 0, lenet_forced_fc_slices());
 }
-// Runs what the plan decides (hipErrorInvalidValue where it has an error).
+// The rule the launch's optimizer options (EMA, Adam / AdamW) break, or null (kernels/lenet_plan.h).
+inline const char* lenet_update_rule(const LenetUpdateArgs& a) {
+  return lenet_update_rule(a.apply_sgd != 0, a.step != nullptr, a.ticket != nullptr, a.mom, a.dampening,
+                           a.nesterov != 0, reinterpret_cast<uintptr_t>(a.ema), a.ema_decay,
+                           reinterpret_cast<uintptr_t>(a.adam_v), a.beta1, a.beta2, a.adam_eps);
+}
+// Runs what the plan decides (hipErrorInvalidValue where it or lenet_update_rule has an error).
 // loss_parts [nparts, 2] are summed in a fixed order into loss_acc[2] (optional).
 // px: the exchange buffer's device view resolved once by the caller (csrc/bindings.cpp),
 // so a launch does no registry lookup; null: looked up from a.exch_id.

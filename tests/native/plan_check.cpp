@@ -3,8 +3,11 @@
 // valid keeps the invariants the kernels' instantiations rely on, over every batch / grid / dtype / request /
 // staging / train-or-eval combination near the thresholds, (b) the engine's default geometry at each
 // threshold is the hand-written table below, and (c) lenet_update's plan is, case by case, what the launcher
-// decided before the plan existed (transcribed below), with the grid invariants update_role relies on.
+// decided before the plan existed (transcribed below), with the grid invariants update_role relies on, and
+// (d) lenet_update_rule accepts and rejects the optimizer options of the table in check_rule, sentence by sentence.
+#include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <initializer_list>
 
 #include "kernels/lenet_plan.h"
@@ -163,6 +166,73 @@ static long check_updates() {
   return valid;
 }
 
+// ---- lenet_update_rule: the optimizer options (EMA, Adam / AdamW).  Four valid launches, then one launch per
+// sentence that breaks exactly that rule, then the float32 edge: the rule judges what the kernel will see.
+struct Opt {
+  const char* what;
+  bool apply_sgd, step, ticket;
+  float mom, dampening;
+  bool nesterov;
+  uintptr_t ema;
+  double ema_decay;
+  uintptr_t adam_v;
+  double beta1, beta2, eps;
+  const char* says;  // a piece of the sentence; null: a valid launch
+};
+
+static void check_rule() {
+  const uintptr_t E = 0x7f0000001000, V = 0x7f0000020000;  // (16-byte aligned addresses; never dereferenced)
+  const Opt table[] = {
+      {"sgd", true, true, true, 0.5f, 0.1f, true, 0, 0.0, 0, 0.0, 0.0, 0.0, nullptr},
+      {"sgd, reduce-only", false, false, false, 0.f, 0.f, false, 0, 0.0, 0, 0.0, 0.0, 0.0, nullptr},
+      {"ema", true, true, true, 0.5f, 0.f, false, E, 0.999, 0, 0.0, 0.0, 0.0, nullptr},
+      {"ema, decay 0", true, false, false, 0.f, 0.f, false, E, 0.0, 0, 0.0, 0.0, 0.0, nullptr},
+      {"adam", true, true, true, 0.f, 0.f, false, 0, 0.0, V, 0.9, 0.999, 1e-8, nullptr},
+      {"adamw (the rule does not see decoupled) with ema, betas 0", true, true, true, 0.f, 0.f, false, E, 0.99, V, 0.0,
+       0.0, 1e-8, nullptr},
+      {"ema on a reduce-only launch", false, true, true, 0.f, 0.f, false, E, 0.9, 0, 0.0, 0.0, 0.0,
+       "ema comes only with apply_sgd"},
+      {"ema_decay 1", true, true, true, 0.f, 0.f, false, E, 1.0, 0, 0.0, 0.0, 0.0, "ema_decay must be in [0, 1)"},
+      {"ema_decay < 0", true, true, true, 0.f, 0.f, false, E, -0.1, 0, 0.0, 0.0, 0.0, "ema_decay must be in [0, 1)"},
+      {"ema off by 4 bytes", true, true, true, 0.f, 0.f, false, E + 4, 0.9, 0, 0.0, 0.0, 0.0,
+       "ema must be 16-byte aligned"},
+      {"adam on a reduce-only launch", false, true, true, 0.f, 0.f, false, 0, 0.0, V, 0.9, 0.999, 1e-8,
+       "Adam comes only with apply_sgd"},
+      {"adam without step", true, false, true, 0.f, 0.f, false, 0, 0.0, V, 0.9, 0.999, 1e-8, "needs step and ticket"},
+      {"adam without ticket", true, true, false, 0.f, 0.f, false, 0, 0.0, V, 0.9, 0.999, 1e-8, "needs step and ticket"},
+      {"adam_v off by 4 bytes", true, true, true, 0.f, 0.f, false, 0, 0.0, V + 4, 0.9, 0.999, 1e-8,
+       "adam_v must be 16-byte aligned"},
+      {"beta1 < 0", true, true, true, 0.f, 0.f, false, 0, 0.0, V, -0.1, 0.999, 1e-8, "beta1 must be in [0, 1)"},
+      {"beta1 1", true, true, true, 0.f, 0.f, false, 0, 0.0, V, 1.0, 0.999, 1e-8, "beta1 must be in [0, 1)"},
+      {"beta2 1", true, true, true, 0.f, 0.f, false, 0, 0.0, V, 0.9, 1.0, 1e-8, "beta2 must be in [0, 1)"},
+      {"eps 0", true, true, true, 0.f, 0.f, false, 0, 0.0, V, 0.9, 0.999, 0.0, "eps must be positive"},
+      {"adam with mom", true, true, true, 0.5f, 0.f, false, 0, 0.0, V, 0.9, 0.999, 1e-8, "mom, dampening and nesterov"},
+      {"adam with dampening", true, true, true, 0.f, 0.1f, false, 0, 0.0, V, 0.9, 0.999, 1e-8,
+       "mom, dampening and nesterov"},
+      {"adam with nesterov", true, true, true, 0.f, 0.f, true, 0, 0.0, V, 0.9, 0.999, 1e-8, "mom, dampening and nesterov"},
+      // below 1 in double, 1.0f in float32 (1 - 2^-30); positive in double, 0.0f in float32
+      {"beta1 rounds to 1", true, true, true, 0.f, 0.f, false, 0, 0.0, V, 0.999999999, 0.999, 1e-8,
+       "beta1 must be in [0, 1)"},
+      {"beta2 rounds to 1", true, true, true, 0.f, 0.f, false, 0, 0.0, V, 0.9, 0.999999999, 1e-8,
+       "beta2 must be in [0, 1)"},
+      {"ema_decay rounds to 1", true, true, true, 0.f, 0.f, false, E, 0.999999999, 0, 0.0, 0.0, 0.0,
+       "ema_decay must be in [0, 1)"},
+      {"eps rounds to 0", true, true, true, 0.f, 0.f, false, 0, 0.0, V, 0.9, 0.999, 1e-50, "eps must be positive"},
+  };
+  int valid = 0;
+  for (const Opt& o : table) {
+    const char* r = lenet_update_rule(o.apply_sgd, o.step, o.ticket, o.mom, o.dampening, o.nesterov, o.ema,
+                                      (float)o.ema_decay, o.adam_v, (float)o.beta1, (float)o.beta2, (float)o.eps);
+    valid += !o.says;
+    if (!o.says) EXPECT(!r, "rule: %s is valid, got '%s'", o.what, r ? r : "");
+    else EXPECT(r && std::strstr(r, o.says), "rule: %s must say '%s', got '%s'", o.what, o.says, r ? r : "(valid)");
+  }
+  EXPECT(valid == 6, "rule: the valid launches");
+  EXPECT(0.999999999 < 1.0 && (float)0.999999999 == 1.0f && 1e-50 > 0.0 && (float)1e-50 == 0.0f, "the float32 edges");
+  // the same options break nothing once the buffer is gone
+  EXPECT(!lenet_update_rule(false, false, false, 0.5f, 0.1f, true, 0, 7.f, 0, 7.f, 7.f, -1.f), "no buffer, no rule");
+}
+
 struct Row {
   int dtype, B;                                  // default grid, split allowed
   int grid, split, staged, tile_staged, rows;    // the geometry
@@ -176,6 +246,7 @@ int main() {
   EXPECT(valid > 1000000, "only %ld valid plans", valid);
   const long updates = check_updates();
   EXPECT(updates > 20000, "only %ld valid update plans", updates);
+  check_rule();
 
   // launches that must stay rejected, each with a message
   EXPECT(lenet_plan(64, 64, kBF16, 2, false, false, false, true, true).error, "kernel 2 off the tile grid");
