@@ -382,11 +382,17 @@ class _MaxPoolRelu(torch.autograd.Function):
 
 
 def max_pool2d_relu(x, k: int = 2, chscale: torch.Tensor | None = None):
-    """relu(max_pool2d(x * chscale, k)) with kernel == stride == k."""
+    """relu(max_pool2d(x, k)) * chscale with kernel == stride == k; ``chscale`` is an fp32 [N*C] per-plane scale.
+
+    The scale multiplies the pooled, rectified value (maxpool_relu_fwd_kernel), which equals
+    relu(max_pool2d(x * chscale, k)) only for scales >= 0 (a Dropout2d mask): a negative scale gives a
+    negative output here, and 0 there.
+    """
     if not x.is_cuda:
+        y = F.relu(F.max_pool2d(x, k))
         if chscale is not None:
-            x = x * chscale.view(x.shape[0], x.shape[1], 1, 1).to(x.dtype)
-        return F.relu(F.max_pool2d(x, k))
+            y = y * chscale.view(x.shape[0], x.shape[1], 1, 1).to(y.dtype)
+        return y
     return _MaxPoolRelu.apply(x, int(k), chscale)
 
 
