@@ -1,5 +1,7 @@
-"""Optimizers: SGD-momentum as one fused HIP kernel over a flat buffer, device-resident LR schedules."""
+"""Optimizers: SGD-momentum as one fused HIP kernel over a flat buffer, Adam / AdamW over a flat buffer on CPU
+parameters, device-resident LR schedules."""
+from .adam import FusedAdam
 from .schedule import LRSchedule
 from .sgd import FusedSGD
 
-__all__ = ["FusedSGD", "LRSchedule"]
+__all__ = ["FusedAdam", "FusedSGD", "LRSchedule"]
