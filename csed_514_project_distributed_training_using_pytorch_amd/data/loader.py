@@ -22,7 +22,8 @@ from .mnist import MNIST_MEAN, MNIST_STD, MNISTData
 class DeviceLoader:
     def __init__(self, data: MNISTData, batch_size: int, sampler=None, shuffle: bool = False,
                  device="cpu", dtype: torch.dtype = torch.float32, drop_last: bool = False,
-                 mean: float = MNIST_MEAN, std: float = MNIST_STD, generator: torch.Generator | None = None):
+                 mean: float = MNIST_MEAN, std: float = MNIST_STD, generator: torch.Generator | None = None,
+                 augment=None):
         self.device = torch.device(device)
         self.data = data.to(self.device)
         self.dataset = self.data  # len(loader.dataset) like the reference
@@ -36,6 +37,10 @@ class DeviceLoader:
         # optional (B, dtype) -> (x, target) buffers to gather into (e.g. a captured training
         # step's static inputs, engine/modular.py bind_loader) or None for fresh tensors
         self.into = None
+        # data/augment.py AffineAugment (enabled): every __iter__ warps the epoch's rows into a private copy of
+        # the images, and batch() gathers from that copy
+        self.augment = augment if augment is not None and augment.enabled else None
+        self.images = self.data.images.clone() if self.augment is not None else self.data.images
 
     def _order(self) -> torch.Tensor:
         if self.sampler is not None:
@@ -61,15 +66,18 @@ class DeviceLoader:
             else:
                 out = torch.empty((B, 1, 28, 28), device=self.device, dtype=self.dtype)
                 lab = torch.empty((B,), device=self.device, dtype=torch.long)
-            _native.ops().gather_normalize(self.data.images, idx, None, B, self.mean, self.std, out, lab,
+            _native.ops().gather_normalize(self.images, idx, None, B, self.mean, self.std, out, lab,
                                            self.data.labels)
             return out, lab
-        x = self.data.images[idx].to(torch.float32).div_(255.0).sub_(self.mean).div_(self.std)
+        x = self.images[idx].to(torch.float32).div_(255.0).sub_(self.mean).div_(self.std)
         return x.view(B, 1, 28, 28).to(self.dtype), self.data.labels[idx]
 
     def __iter__(self):
         order = self._order().to(self.device)
         n = order.numel()
+        if self.augment is not None:
+            self.augment.apply(self.data.images, self.images, idx=order)
+            self.augment.epoch += 1
         for s in range(0, n, self.batch_size):
             e = min(n, s + self.batch_size)
             if self.drop_last and e - s < self.batch_size:

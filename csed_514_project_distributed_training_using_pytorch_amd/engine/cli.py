@@ -24,7 +24,7 @@ import time
 import torch
 
 from .. import ops
-from ..data import DeviceLoader, get_mnist
+from ..data import AffineAugment, DeviceLoader, get_mnist
 from ..models import Net
 from ..parallel.comm import all_reduce_max, barrier, destroy, init_distributed, replica_checksum
 from ..parallel.sampler import ShardSampler
@@ -61,6 +61,22 @@ def _common_flags(ap: argparse.ArgumentParser) -> None:
                          "optimizer step (on the device, inside the update kernel): one more line with its loss "
                          "and accuracy after each validation line, and results/ema.pth next to results/model.pth "
                          "(default: off)")
+    ap.add_argument("--augment-shift", type=float, default=0.0, metavar="PX",
+                    help="random shift of every training digit by up to PX pixels in x and y, drawn anew each "
+                         "epoch (data.AffineAugment: one kernel per epoch writes the augmented train set)")
+    ap.add_argument("--augment-rotate", type=float, default=0.0, metavar="DEG",
+                    help="random rotation by up to DEG degrees either way")
+    ap.add_argument("--augment-scale", type=float, default=0.0, metavar="F",
+                    help="random zoom by a factor in [1 - F, 1 + F], 0 <= F < 1")
+
+
+def _make_augment(args):
+    """The --augment-* flags as a data.AffineAugment seeded by --seed, or None when all three are 0."""
+    try:
+        aug = AffineAugment(args.augment_shift, args.augment_rotate, args.augment_scale, seed=args.seed)
+    except ValueError as e:
+        raise SystemExit(f"--augment-shift / --augment-rotate / --augment-scale: {e}")
+    return aug if aug.enabled else None
 
 
 def _optimizer_flags(ap: argparse.ArgumentParser) -> None:
@@ -224,6 +240,10 @@ def single_main(argv=None) -> int:
     results = os.path.join(out, "results")
     sched_path = os.path.join(results, "lr_schedule.pth")
     ema_path = os.path.join(results, "ema.pth")
+    aug_path = os.path.join(results, "augment.pth")  # {"epoch": the augmenter's} of the run's last checkpoint
+    aug = _make_augment(args)
+    if aug is not None and args.resume and os.path.exists(aug_path):
+        aug.epoch = int(torch.load(aug_path, weights_only=True)["epoch"])  # (the resumed epoch's images again)
     sched = _make_schedule(args, (n_train + args.batch_size - 1) // args.batch_size)
     if args.resume:
         _check_resume_optimizer(args, os.path.join(results, "optimizer.pth"))
@@ -246,6 +266,7 @@ def single_main(argv=None) -> int:
             saved = checkpoint.load_ema(ema_path) if args.resume else None
             if saved is not None:
                 eng.load_ema_state_dict(saved)
+        eng.set_augment(aug)
 
         def test():
             lsum, correct = eng.evaluate(test_set)
@@ -263,6 +284,8 @@ def single_main(argv=None) -> int:
                 checkpoint._atomic_save(sched.state_dict(), sched_path)
             if args.ema_decay is not None:
                 checkpoint.save_ema(eng.ema_state_dict(), ema_path)
+            if aug is not None:  # (advanced when the epoch started: the epoch a resumed run starts with is this one)
+                checkpoint._atomic_save({"epoch": aug.epoch - 1}, aug_path)
 
         nb = (n_train + args.batch_size - 1) // args.batch_size
         test()
@@ -322,7 +345,7 @@ def single_main(argv=None) -> int:
             if saved is not None:
                 tr.opt.load_ema_state_dict(saved)
         train_loader = DeviceLoader(train, args.batch_size, shuffle=True, device=dev,
-                                    dtype=ops.compute_dtype() if dev.type == "cuda" else torch.float32)
+                                    dtype=ops.compute_dtype() if dev.type == "cuda" else torch.float32, augment=aug)
         tr.bind_loader(train_loader)
 
         def test():
@@ -351,6 +374,8 @@ def single_main(argv=None) -> int:
                         checkpoint._atomic_save(sched.state_dict(), sched_path)
                     if args.ema_decay is not None:
                         checkpoint.save_ema(tr.opt.ema_state_dict(), ema_path)
+                    if aug is not None:
+                        checkpoint._atomic_save({"epoch": aug.epoch - 1}, aug_path)
             test()
 
     if not args.no_plot:
@@ -432,6 +457,7 @@ def dist_main(argv=None) -> int:
     sampler = ShardSampler(len(train), ctx.world_size, ctx.rank, shuffle=True, seed=args.sampler_seed)
     test_loader = DeviceLoader(test_set, args.test_batch_size, shuffle=True, device=dev)
     net = Net().to(dev)
+    aug = _make_augment(args)  # (every rank warps its own shard; the maps are keyed by dataset row, not by rank)
     hist = metrics.LossHistory()
     # ref train_dist.py:89,153: counters in units of the whole training set (len(dataset))
     hist.test_counter = [i * len(train) for i in range(args.epochs)]
@@ -453,6 +479,7 @@ def dist_main(argv=None) -> int:
         if args.ema_decay is not None:  # (after the constructor's parameter broadcast: the same start everywhere)
             eng.set_ema(args.ema_decay)
         ema_sd = eng.ema_state_dict if args.ema_decay is not None else None
+        eng.set_augment(aug)
         sampler.set_epoch(0)
         order = sampler.indices()
         i = 0
@@ -465,6 +492,8 @@ def dist_main(argv=None) -> int:
             if ipc_live and args.inject_exchange_fault == i and ctx.rank == ctx.world_size - 1:
                 eng.inject_exchange_fault()
             n_hist = (len(hist.train_losses), len(hist.train_counter))
+            if aug is not None:
+                aug.epoch = i  # (an epoch re-run after an exchange time-out sees the same images)
             eng.set_epoch_order(order)
             epoch_order = order
             steps, full, rem = eng.steps_per_epoch(), eng.full_steps(), eng.tail_size()
@@ -535,7 +564,7 @@ def dist_main(argv=None) -> int:
                             weight_decay=args.weight_decay)
         _modular_adam(args, tr, net)
         loader = DeviceLoader(train, per_rank, sampler=sampler, device=dev,
-                              dtype=ops.compute_dtype() if dev.type == "cuda" else torch.float32)
+                              dtype=ops.compute_dtype() if dev.type == "cuda" else torch.float32, augment=aug)
         sched = _make_schedule(args, len(loader))
         if sched is not None:
             tr.opt.set_lr_schedule(sched)

@@ -296,6 +296,8 @@ class FusedLeNetTrainer:
         self.ema: torch.Tensor | None = None  # the parameters' moving average (set_ema), or None: off
         self.ema_decay = 0.0
         self._ema_wimg: torch.Tensor | None = None  # its weight image, packed for evaluate(ema=True)
+        self.augment = None  # data.AffineAugment (set_augment), or None: the training launches read train_data.images
+        self._aug_images: torch.Tensor | None = None  # the epoch's augmented copy of train_data.images
         self.native_max = native_max_steps()
         # which training kernel a step asks for: 0 auto (the sample-tile kernel, csrc/kernels/lenet_tile.hip,
         # for large 16-bit per-rank batches), 1 the per-sample lenet_train, 2 the sample-tile kernel
@@ -472,6 +474,7 @@ class FusedLeNetTrainer:
             if host.numel() == self.perm.numel():  # straight into the captured buffer: one copy
                 self.perm.copy_(host, non_blocking=True)
                 _native.zero_(self.cursor)
+                self._augment_epoch()
                 self._stage_current()
                 return
             order = torch.empty(host.shape, dtype=torch.long, device=self.device)
@@ -484,12 +487,26 @@ class FusedLeNetTrainer:
             self.invalidate()  # captured pointers refer to the old buffer
             self.perm = order
         _native.zero_(self.cursor)
+        self._augment_epoch()
         self._stage_current()
+
+    @property
+    def train_images(self) -> torch.Tensor:
+        """The uint8 rows the training launches gather: the train set's, or under set_augment the epoch's
+        augmented copy (evaluation always reads the set it is given)."""
+        return self.train_data.images if self._aug_images is None else self._aug_images
+
+    def _augment_epoch(self) -> None:
+        """Warp the rows of the new epoch order into the augmented copy (one launch, on the stream the
+        staging gather and the steps follow on) and advance the augmenter's epoch."""
+        if self._aug_images is not None:
+            self.augment.apply(self.train_data.images, self._aug_images, idx=self.perm)
+            self.augment.epoch += 1
 
     def _stage_current(self) -> None:
         """Gather the batch at the cursor into the staging buffers (epoch start)."""
         if self.xstage is not None:
-            torch.ops.csed.lenet_stage(self.train_data.images, self.train_data.labels, self.perm, self.cursor,
+            torch.ops.csed.lenet_stage(self.train_images, self.train_data.labels, self.perm, self.cursor,
                                        self.B, self.xstage, self.lstage)
 
     def uses_tile_kernel(self, B: int | None = None, grid: int | None = None) -> bool:
@@ -537,7 +554,7 @@ class FusedLeNetTrainer:
         grad_scale = self.grad_scale if grad_scale is None else grad_scale
         in_kernel = self.fp32 if scale_in_kernel is None else scale_in_kernel
         return TrainArgs(
-            images=self.train_data.images, labels=self.train_data.labels, perm=self.perm if perm is None else perm,
+            images=self.train_images, labels=self.train_data.labels, perm=self.perm if perm is None else perm,
             cursor=cursor, B=B, rank=self.ctx.rank if rank is None else rank, wimg=self.wimg, params=self.flat.data,
             slab=self.slab, vslab=self.vslab, loss_parts=self.loss_parts, grad_scale=grad_scale if in_kernel else 1.0,
             mean=MNIST_MEAN, std=MNIST_STD, drop_p=self.drop_p, seed=self.seed, rng_offset=self.rng_offset, grid=grid,
@@ -951,6 +968,22 @@ class FusedLeNetTrainer:
                 self.ema = _native.zeros(self.flat.data.shape, torch.float32, self.device)
             self.ema.copy_(self.flat.data)
             self.ema_decay = float(decay)
+        self.invalidate()
+
+    def set_augment(self, augment) -> None:
+        """Train on randomly shifted / rotated / scaled digits (``data.AffineAugment``): from the next
+        set_epoch_order on, every epoch's rows are warped once, by one ``csed::augment_affine`` launch, into a
+        device copy of the train images, and the training launches gather from that copy.  Its address does not
+        change from epoch to epoch, so the captured graphs stay valid.  None, or an augmenter whose maxima are
+        all zero, restores the plain path: the same pointers and launches as without this call.  Captured
+        graphs and the executor's argument blocks hold the other image pointer: dropped, as in set_ema."""
+        on = augment is not None and augment.enabled
+        self.augment = augment if on else None
+        if not on:
+            self._aug_images = None
+        elif self._aug_images is None:  # (a device-to-device memcpy: rows no epoch order names stay plain)
+            self._aug_images = torch.empty_like(self.train_data.images)
+            self._aug_images.copy_(self.train_data.images)
         self.invalidate()
 
     def ema_state_dict(self) -> dict:

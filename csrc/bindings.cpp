@@ -84,6 +84,44 @@ void gather_normalize(const Tensor& src, const Tensor& idx, const optional<Tenso
                                           cur_stream(src)));
 }
 
+// Random affine augmentation of uint8 [N, 784] (or [N, 28, 28]) rows, kernels/augment.hip.  Row idx[i] (idx
+// absent: row i) of src is warped into the same row of dst; rows not named keep what dst held.  Like
+// gather_normalize the op does not range-check the index values on the host (no synchronisation: it is
+// legal under graph capture); the kernel skips a row whose index is outside [0, N).
+void augment_affine(const Tensor& src, Tensor& dst, const optional<Tensor>& idx, const optional<Tensor>& theta_in,
+                    const optional<Tensor>& theta_out, int64_t seed, int64_t epoch, double max_shift,
+                    double max_rot_deg, double max_scale) {
+  dev(src, "src"); dev(dst, "dst");
+  TORCH_CHECK(src.scalar_type() == at::kByte && dst.scalar_type() == at::kByte, "augment_affine: src and dst are uint8");
+  TORCH_CHECK(src.sizes() == dst.sizes() && src.device() == dst.device(), "augment_affine: src and dst differ in shape or device");
+  TORCH_CHECK(src.dim() >= 2 && src.numel() == src.size(0) * 784, "augment_affine: rows of 784 bytes ([N, 784] or [N, 28, 28])");
+  const int64_t N = src.size(0);
+  const auto* s0 = src.data_ptr<uint8_t>();
+  auto* d0 = dst.data_ptr<uint8_t>();
+  TORCH_CHECK(s0 + src.numel() <= d0 || d0 + dst.numel() <= s0, "augment_affine: src and dst overlap");
+  TORCH_CHECK(((uintptr_t)s0 | (uintptr_t)d0) % 16 == 0, "augment_affine: src and dst must be 16-byte aligned");
+  int64_t M = N;
+  if (idx.has_value()) {
+    dev(*idx, "idx");
+    TORCH_CHECK(idx->scalar_type() == at::kLong && idx->dim() == 1, "augment_affine: idx is int64 [M]");
+    M = idx->numel();
+  }
+  TORCH_CHECK(M < (int64_t(1) << 31), "augment_affine: too many rows");
+  for (const auto* t : {&theta_in, &theta_out}) {
+    if (!t->has_value()) continue;
+    dev(**t, "theta");
+    TORCH_CHECK((*t)->scalar_type() == at::kFloat && (*t)->dim() == 2 && (*t)->size(0) == M && (*t)->size(1) == 6,
+                "augment_affine: theta_in / theta_out are float32 [M, 6] with M = ", M);
+  }
+  TORCH_CHECK(seed >= 0 && epoch >= 0, "augment_affine: seed and epoch are >= 0");
+  TORCH_CHECK(max_shift >= 0 && max_rot_deg >= 0 && max_scale >= 0 && max_scale < 1,
+              "augment_affine: expected max_shift >= 0, max_rot_deg >= 0 and 0 <= max_scale < 1");
+  const c10::DeviceGuard g(src.device());
+  CHECK_HIP(csed::launch_augment_affine(s0, d0, optpt<int64_t>(idx), optpt<float>(theta_in), optpt<float>(theta_out),
+                                        N, M, (uint64_t)seed, (uint64_t)epoch, (float)max_shift, (float)max_rot_deg,
+                                        (float)max_scale, cur_stream(src)));
+}
+
 // ------------------------------------------------------------- optimizer
 // A device-resident learning-rate schedule's table / position pair (optim/schedule.py), both or neither: the
 // tensors.  (A table without entries is sgd_flat's own check below and, for lenet_update, the plan's.)
@@ -1171,6 +1209,8 @@ TORCH_LIBRARY(csed, m) {
         "float std, Tensor(a!) out_parts, Tensor(b!)? logp_out, int mfma_dtype, int kernel=0) -> ()");
   m.def("gather_normalize(Tensor src, Tensor idx, Tensor? cursor, int B, float mean, float std, Tensor(a!) out, "
         "Tensor(b!)? labels_out, Tensor? labels_src) -> ()");
+  m.def("augment_affine(Tensor src, Tensor(a!) dst, Tensor? idx, Tensor? theta_in, Tensor(b!)? theta_out, int seed, "
+        "int epoch, float max_shift, float max_rot_deg, float max_scale) -> ()");
   m.def("sgd_flat(Tensor(a!) p, Tensor g, Tensor(b!) buf, float lr, float momentum, float dampening, "
         "float weight_decay, bool nesterov, float grad_scale, Tensor(c!) step, Tensor(d!) ticket, "
         "Tensor? lr_table=None, Tensor(e!)? lr_pos=None) -> ()");
@@ -1220,6 +1260,7 @@ TORCH_LIBRARY(csed, m) {
 
 TORCH_LIBRARY_IMPL(csed, CUDA, m) {
   m.impl("gather_normalize", &gather_normalize);
+  m.impl("augment_affine", &augment_affine);
   m.impl("sgd_flat", &sgd_flat);
   m.impl("log_softmax_fwd", &log_softmax_fwd);
   m.impl("log_softmax_bwd", &log_softmax_bwd);

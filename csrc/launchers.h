@@ -23,6 +23,15 @@ hipError_t launch_gather_normalize(const uint8_t* src, const int64_t* idx, const
                                    void* out, int out_dtype, int64_t* labels_out,
                                    const int64_t* labels_src, hipStream_t s);
 
+// Random affine augmentation (kernels/augment.hip): row r = idx[i] (idx null: r = i), i < M, of the
+// uint8 [N, 784] set src is warped into the same row of dst, by theta_in[i] (six floats: the inverse
+// map) or, theta_in null, by the map drawn from philox_uniform(seed, epoch, 4 r + 0..3) within the three
+// maxima; theta_out[i] (optional) gets the map used.  A row whose index is outside [0, N) is skipped.
+// src, dst: 16-byte aligned, distinct.
+hipError_t launch_augment_affine(const uint8_t* src, uint8_t* dst, const int64_t* idx, const float* theta_in,
+                                 float* theta_out, int64_t N, int64_t M, uint64_t seed, uint64_t epoch,
+                                 float max_shift, float max_rot_deg, float max_scale, hipStream_t s);
+
 // ----------------------------------------------------------- optimizer ----
 // SGD with momentum over a flat fp32 buffer (torch.optim.SGD semantics).
 // step[0] == 0 means "momentum buffer not yet initialised" (buf = g).
