@@ -13,6 +13,9 @@ image contribute 0; the byte is ``min(255, floor(v + 0.5))``.  Row r draws
 ``u_j = philox_uniform(seed, epoch, 4 r + j)`` and uses dx = (2 u0 - 1) max_shift, dy likewise from u1,
 phi = (2 u2 - 1) max_rot_deg pi / 180, s = 1 + (2 u3 - 1) max_scale, a = d = cos(phi) / s,
 b = -cc = sin(phi) / s, e = -dx, f = -dy.
+
+``ElasticAugment`` adds a per-row smoothed random displacement field to the sampling coordinate
+(``csed::augment_elastic``, csrc/kernels/augment_elastic.hip) behind the same interface.
 """
 from __future__ import annotations
 
@@ -77,14 +80,105 @@ class AffineAugment:
         return theta if return_theta else None
 
 
-def _warp_cpu(img: torch.Tensor, theta: torch.Tensor) -> torch.Tensor:
-    """uint8 [M, 784] warped by float32 [M, 6] inverse maps, in float64."""
+ELASTIC_STREAM = 1 << 40  # first Philox index of the raw displacement fields (the affine draws end below 2^33)
+
+
+def gauss_table(sigma: float) -> torch.Tensor:
+    """The definition's G: float32 [32, 32], the 28 x 28 matrix exp(-(i - k)^2 / (2 sigma^2)) / Z inside zero
+    padding, Z the sum over d = -27 .. 27 (one normalisation for every row), built in float64."""
+    import numpy as np
+
+    d = np.arange(-27, 28, dtype=np.float64)
+    z = np.exp(-d * d / (2.0 * sigma * sigma)).sum()
+    i = np.arange(28, dtype=np.float64)
+    g = np.zeros((32, 32), dtype=np.float32)
+    g[:28, :28] = np.exp(-(i[:, None] - i[None, :]) ** 2 / (2.0 * sigma * sigma)) / z
+    return torch.from_numpy(g)
+
+
+class ElasticAugment(AffineAugment):
+    """Elastic deformation (Simard, Steinkraus, Platt 2003) on top of the affine map: every row gets its own
+    random displacement field, smoothed by a Gaussian of ``sigma`` pixels and scaled by ``alpha`` pixels
+    (docs/ARCHITECTURE.md "Elastic augmentation").  With ``U_c[i][j] = 2 philox_uniform(seed, epoch,
+    2^40 + 1568 r + 784 c + 28 i + j) - 1`` (c = 0: x, c = 1: y; i = pixel row) the field is
+    ``D_c = alpha (G U_c G)`` and pixel (x, y) samples at the affine coordinate plus ``(D_0[y][x], D_1[y][x])``.
+    ``alpha == 0`` is ``AffineAugment``, launch for launch."""
+
+    CPU_CHUNK = 512  # rows per pass of the CPU path (1,568 float64 Philox draws per row)
+
+    def __init__(self, alpha: float, sigma: float = 4.0, max_shift: float = 0.0, max_rot_deg: float = 0.0,
+                 max_scale: float = 0.0, seed: int | None = None):
+        super().__init__(max_shift, max_rot_deg, max_scale, seed)
+        alpha, sigma = float(alpha), float(sigma)
+        if not (math.isfinite(alpha) and alpha >= 0 and math.isfinite(sigma) and sigma > 0):
+            raise ValueError(f"elastic augmentation alpha {alpha} px, sigma {sigma} px: expected a finite "
+                             f"alpha >= 0 and a finite sigma > 0")
+        self.alpha, self.sigma = alpha, sigma
+        self._gauss: dict[torch.device, torch.Tensor] = {}
+
+    @property
+    def enabled(self) -> bool:
+        return self.alpha > 0 or super().enabled
+
+    def gauss(self, device) -> torch.Tensor:
+        """The float32 [32, 32] table G on ``device`` (built once per device)."""
+        device = torch.device(device)
+        if device not in self._gauss:
+            self._gauss[device] = gauss_table(self.sigma).to(device)
+        return self._gauss[device]
+
+    def draw_disp(self, rows: torch.Tensor) -> torch.Tensor:
+        """The float32 [M, 2, 28, 28] fields of dataset rows ``rows`` at the current epoch, on the host in
+        float64 (the CPU path's; the kernel draws the same U and smooths it in fp32 on the matrix cores)."""
+        import numpy as np
+
+        r = rows.detach().cpu().numpy().astype(np.uint64)
+        at = np.uint64(ELASTIC_STREAM) + np.uint64(1568) * r[:, None] + np.arange(1568, dtype=np.uint64)
+        u = torch.from_numpy(2.0 * philox_uniform_reference(self.seed, self.epoch, at) - 1.0).view(-1, 2, 28, 28)
+        g = self.gauss("cpu")[:28, :28].to(torch.float64)
+        return (self.alpha * (g @ u @ g)).to(torch.float32)
+
+    def apply(self, src: torch.Tensor, dst: torch.Tensor, idx: torch.Tensor | None = None,
+              theta: torch.Tensor | None = None, disp: torch.Tensor | None = None, return_theta: bool = False,
+              return_disp: bool = False):
+        """``AffineAugment.apply`` with the displacement field: drawn at ``self.epoch``, or ``disp`` (float32
+        [M, 2, 28, 28], one field pair per entry of ``idx``: a plain flow-field warp).  Returns the float32 maps
+        (``return_theta``), the float32 fields used (``return_disp``), both as a pair, or None.  On a GPU one
+        launch of ``csed::augment_elastic``; on the CPU the definition in float64 torch ops."""
+        if self.alpha == 0 and disp is None and not return_disp:
+            return super().apply(src, dst, idx, theta, return_theta)
+        M = src.shape[0] if idx is None else idx.numel()
+        if src.device.type == "cuda":
+            from ..ops import _native
+
+            tout = torch.empty((M, 6), dtype=torch.float32, device=src.device) if return_theta else None
+            dout = torch.empty((M, 2, 28, 28), dtype=torch.float32, device=src.device) if return_disp else None
+            _native.ops().augment_elastic(src, dst, idx, theta, tout, disp, dout, self.gauss(src.device), self.seed,
+                                          self.epoch, self.max_shift, self.max_rot_deg, self.max_scale, self.alpha)
+        else:
+            rows = torch.arange(src.shape[0]) if idx is None else idx.to(torch.long)
+            tout = self.draw(rows) if theta is None else theta.to(torch.float32)
+            dout = torch.empty((M, 2, 28, 28), dtype=torch.float32)
+            for s in range(0, M, self.CPU_CHUNK):
+                c = slice(s, s + self.CPU_CHUNK)
+                dout[c] = self.draw_disp(rows[c]) if disp is None else disp[c].to(torch.float32)
+                dst.view(-1, 784)[rows[c]] = _warp_cpu(src.view(-1, 784)[rows[c]], tout[c], dout[c])
+        out = tuple(t for t, want in ((tout, return_theta), (dout, return_disp)) if want)
+        return None if not out else out[0] if len(out) == 1 else out
+
+
+def _warp_cpu(img: torch.Tensor, theta: torch.Tensor, disp: torch.Tensor | None = None) -> torch.Tensor:
+    """uint8 [M, 784] warped by float32 [M, 6] inverse maps (plus float32 [M, 2, 28, 28] displacements), in
+    float64."""
     M, c = img.shape[0], 13.5
     th = theta.to(torch.float64).view(M, 6, 1)
     p = torch.arange(784)
     x, y = (p % 28).to(torch.float64) - c, (p // 28).to(torch.float64) - c
     sx = th[:, 0] * x + th[:, 1] * y + c + th[:, 2]
     sy = th[:, 3] * x + th[:, 4] * y + c + th[:, 5]
+    if disp is not None:
+        d = disp.to(torch.float64).view(M, 2, 784)
+        sx, sy = sx + d[:, 0], sy + d[:, 1]
     pad = torch.zeros((M, 31, 31), dtype=torch.float64)  # cells -1 .. 29: a zero border, as in the kernel
     pad[:, 1:29, 1:29] = img.view(M, 28, 28).to(torch.float64)
     sx, sy = sx.clamp(-1.0, 28.0), sy.clamp(-1.0, 28.0)

@@ -24,7 +24,7 @@ import time
 import torch
 
 from .. import ops
-from ..data import AffineAugment, DeviceLoader, get_mnist
+from ..data import AffineAugment, DeviceLoader, ElasticAugment, get_mnist
 from ..models import Net
 from ..parallel.comm import all_reduce_max, barrier, destroy, init_distributed, replica_checksum
 from ..parallel.sampler import ShardSampler
@@ -68,14 +68,26 @@ def _common_flags(ap: argparse.ArgumentParser) -> None:
                     help="random rotation by up to DEG degrees either way")
     ap.add_argument("--augment-scale", type=float, default=0.0, metavar="F",
                     help="random zoom by a factor in [1 - F, 1 + F], 0 <= F < 1")
+    ap.add_argument("--augment-elastic", type=float, default=0.0, metavar="ALPHA",
+                    help="elastic deformation (Simard et al. 2003): every digit is resampled through its own random "
+                         "displacement field, smoothed by a Gaussian and scaled to ALPHA pixels, on top of the "
+                         "affine flags (data.ElasticAugment; try 34 with sigma 4)")
+    ap.add_argument("--augment-elastic-sigma", type=float, default=4.0, metavar="SIGMA",
+                    help="the Gaussian's standard deviation in pixels (default 4.0)")
 
 
 def _make_augment(args):
-    """The --augment-* flags as a data.AffineAugment seeded by --seed, or None when all three are 0."""
+    """The --augment-* flags as a data.AffineAugment (data.ElasticAugment under --augment-elastic) seeded by
+    --seed, or None when nothing is switched on."""
+    affine = (args.augment_shift, args.augment_rotate, args.augment_scale)
     try:
-        aug = AffineAugment(args.augment_shift, args.augment_rotate, args.augment_scale, seed=args.seed)
+        if args.augment_elastic != 0 or args.augment_elastic_sigma != 4.0:
+            aug = ElasticAugment(args.augment_elastic, args.augment_elastic_sigma, *affine, seed=args.seed)
+        else:
+            aug = AffineAugment(*affine, seed=args.seed)
     except ValueError as e:
-        raise SystemExit(f"--augment-shift / --augment-rotate / --augment-scale: {e}")
+        raise SystemExit(f"--augment-shift / --augment-rotate / --augment-scale / --augment-elastic / "
+                         f"--augment-elastic-sigma: {e}")
     return aug if aug.enabled else None
 
 

@@ -6,6 +6,7 @@
 // host or synchronises, so every op is safe inside torch.cuda.graph capture
 // (= hipStreamBeginCapture).
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <vector>
 #include <ATen/ATen.h>
@@ -84,6 +85,37 @@ void gather_normalize(const Tensor& src, const Tensor& idx, const optional<Tenso
                                           cur_stream(src)));
 }
 
+// The argument checks both augmentation ops share; returns M, the number of rows the launch names.
+int64_t check_augment(const char* op, const Tensor& src, const Tensor& dst, const optional<Tensor>& idx,
+                      const optional<Tensor>& theta_in, const optional<Tensor>& theta_out, int64_t seed,
+                      int64_t epoch, double max_shift, double max_rot_deg, double max_scale) {
+  dev(src, "src"); dev(dst, "dst");
+  TORCH_CHECK(src.scalar_type() == at::kByte && dst.scalar_type() == at::kByte, op, ": src and dst are uint8");
+  TORCH_CHECK(src.sizes() == dst.sizes() && src.device() == dst.device(), op, ": src and dst differ in shape or device");
+  TORCH_CHECK(src.dim() >= 2 && src.numel() == src.size(0) * 784, op, ": rows of 784 bytes ([N, 784] or [N, 28, 28])");
+  const auto* s0 = src.data_ptr<uint8_t>();
+  const auto* d0 = dst.data_ptr<uint8_t>();
+  TORCH_CHECK(s0 + src.numel() <= d0 || d0 + dst.numel() <= s0, op, ": src and dst overlap");
+  TORCH_CHECK(((uintptr_t)s0 | (uintptr_t)d0) % 16 == 0, op, ": src and dst must be 16-byte aligned");
+  int64_t M = src.size(0);
+  if (idx.has_value()) {
+    dev(*idx, "idx");
+    TORCH_CHECK(idx->scalar_type() == at::kLong && idx->dim() == 1, op, ": idx is int64 [M]");
+    M = idx->numel();
+  }
+  TORCH_CHECK(M < (int64_t(1) << 31), op, ": too many rows");
+  for (const auto* t : {&theta_in, &theta_out}) {
+    if (!t->has_value()) continue;
+    dev(**t, "theta");
+    TORCH_CHECK((*t)->scalar_type() == at::kFloat && (*t)->dim() == 2 && (*t)->size(0) == M && (*t)->size(1) == 6,
+                op, ": theta_in / theta_out are float32 [M, 6] with M = ", M);
+  }
+  TORCH_CHECK(seed >= 0 && epoch >= 0, op, ": seed and epoch are >= 0");
+  TORCH_CHECK(max_shift >= 0 && max_rot_deg >= 0 && max_scale >= 0 && max_scale < 1,
+              op, ": expected max_shift >= 0, max_rot_deg >= 0 and 0 <= max_scale < 1");
+  return M;
+}
+
 // Random affine augmentation of uint8 [N, 784] (or [N, 28, 28]) rows, kernels/augment.hip.  Row idx[i] (idx
 // absent: row i) of src is warped into the same row of dst; rows not named keep what dst held.  Like
 // gather_normalize the op does not range-check the index values on the host (no synchronisation: it is
@@ -91,35 +123,44 @@ void gather_normalize(const Tensor& src, const Tensor& idx, const optional<Tenso
 void augment_affine(const Tensor& src, Tensor& dst, const optional<Tensor>& idx, const optional<Tensor>& theta_in,
                     const optional<Tensor>& theta_out, int64_t seed, int64_t epoch, double max_shift,
                     double max_rot_deg, double max_scale) {
-  dev(src, "src"); dev(dst, "dst");
-  TORCH_CHECK(src.scalar_type() == at::kByte && dst.scalar_type() == at::kByte, "augment_affine: src and dst are uint8");
-  TORCH_CHECK(src.sizes() == dst.sizes() && src.device() == dst.device(), "augment_affine: src and dst differ in shape or device");
-  TORCH_CHECK(src.dim() >= 2 && src.numel() == src.size(0) * 784, "augment_affine: rows of 784 bytes ([N, 784] or [N, 28, 28])");
-  const int64_t N = src.size(0);
-  const auto* s0 = src.data_ptr<uint8_t>();
-  auto* d0 = dst.data_ptr<uint8_t>();
-  TORCH_CHECK(s0 + src.numel() <= d0 || d0 + dst.numel() <= s0, "augment_affine: src and dst overlap");
-  TORCH_CHECK(((uintptr_t)s0 | (uintptr_t)d0) % 16 == 0, "augment_affine: src and dst must be 16-byte aligned");
-  int64_t M = N;
-  if (idx.has_value()) {
-    dev(*idx, "idx");
-    TORCH_CHECK(idx->scalar_type() == at::kLong && idx->dim() == 1, "augment_affine: idx is int64 [M]");
-    M = idx->numel();
-  }
-  TORCH_CHECK(M < (int64_t(1) << 31), "augment_affine: too many rows");
-  for (const auto* t : {&theta_in, &theta_out}) {
-    if (!t->has_value()) continue;
-    dev(**t, "theta");
-    TORCH_CHECK((*t)->scalar_type() == at::kFloat && (*t)->dim() == 2 && (*t)->size(0) == M && (*t)->size(1) == 6,
-                "augment_affine: theta_in / theta_out are float32 [M, 6] with M = ", M);
-  }
-  TORCH_CHECK(seed >= 0 && epoch >= 0, "augment_affine: seed and epoch are >= 0");
-  TORCH_CHECK(max_shift >= 0 && max_rot_deg >= 0 && max_scale >= 0 && max_scale < 1,
-              "augment_affine: expected max_shift >= 0, max_rot_deg >= 0 and 0 <= max_scale < 1");
+  const int64_t M = check_augment("augment_affine", src, dst, idx, theta_in, theta_out, seed, epoch, max_shift,
+                                  max_rot_deg, max_scale);
   const c10::DeviceGuard g(src.device());
-  CHECK_HIP(csed::launch_augment_affine(s0, d0, optpt<int64_t>(idx), optpt<float>(theta_in), optpt<float>(theta_out),
-                                        N, M, (uint64_t)seed, (uint64_t)epoch, (float)max_shift, (float)max_rot_deg,
+  CHECK_HIP(csed::launch_augment_affine(src.data_ptr<uint8_t>(), dst.data_ptr<uint8_t>(), optpt<int64_t>(idx),
+                                        optpt<float>(theta_in), optpt<float>(theta_out), src.size(0), M,
+                                        (uint64_t)seed, (uint64_t)epoch, (float)max_shift, (float)max_rot_deg,
                                         (float)max_scale, cur_stream(src)));
+}
+
+// Elastic augmentation, kernels/augment_elastic.hip: augment_affine's rows, idx and theta, plus a per-pixel
+// displacement of the sampling coordinate -- disp_in (float32 [M, 2, 28, 28], x then y), or alpha (G U G) of the
+// row's own Philox field U with gauss the float32 [32, 32] zero-padded Gaussian matrix (data.ElasticAugment builds
+// it).  disp_out gets the field used.
+void augment_elastic(const Tensor& src, Tensor& dst, const optional<Tensor>& idx, const optional<Tensor>& theta_in,
+                     const optional<Tensor>& theta_out, const optional<Tensor>& disp_in,
+                     const optional<Tensor>& disp_out, const Tensor& gauss, int64_t seed, int64_t epoch,
+                     double max_shift, double max_rot_deg, double max_scale, double alpha) {
+  const int64_t M = check_augment("augment_elastic", src, dst, idx, theta_in, theta_out, seed, epoch, max_shift,
+                                  max_rot_deg, max_scale);
+  for (const auto* t : {&disp_in, &disp_out}) {
+    if (!t->has_value()) continue;
+    dev(**t, "disp");
+    TORCH_CHECK((*t)->scalar_type() == at::kFloat && (*t)->sizes() == at::IntArrayRef({M, 2, 28, 28}) &&
+                    (*t)->device() == src.device() && (uintptr_t)(*t)->data_ptr() % 16 == 0,
+                "augment_elastic: disp_in / disp_out are float32 [M, 2, 28, 28] on src's device, 16-byte aligned, "
+                "with M = ", M);
+  }
+  dev(gauss, "gauss");
+  TORCH_CHECK(gauss.scalar_type() == at::kFloat && gauss.sizes() == at::IntArrayRef({32, 32}) &&
+                  gauss.device() == src.device() && (uintptr_t)gauss.data_ptr() % 16 == 0,
+              "augment_elastic: gauss is float32 [32, 32] on src's device, 16-byte aligned");
+  TORCH_CHECK(std::isfinite(alpha) && alpha >= 0, "augment_elastic: alpha is finite and >= 0");
+  const c10::DeviceGuard g(src.device());
+  CHECK_HIP(csed::launch_augment_elastic(src.data_ptr<uint8_t>(), dst.data_ptr<uint8_t>(), optpt<int64_t>(idx),
+                                         optpt<float>(theta_in), optpt<float>(theta_out), optpt<float>(disp_in),
+                                         optpt<float>(disp_out), gauss.data_ptr<float>(), src.size(0), M,
+                                         (uint64_t)seed, (uint64_t)epoch, (float)max_shift, (float)max_rot_deg,
+                                         (float)max_scale, (float)alpha, cur_stream(src)));
 }
 
 // ------------------------------------------------------------- optimizer
@@ -1211,6 +1252,9 @@ TORCH_LIBRARY(csed, m) {
         "Tensor(b!)? labels_out, Tensor? labels_src) -> ()");
   m.def("augment_affine(Tensor src, Tensor(a!) dst, Tensor? idx, Tensor? theta_in, Tensor(b!)? theta_out, int seed, "
         "int epoch, float max_shift, float max_rot_deg, float max_scale) -> ()");
+  m.def("augment_elastic(Tensor src, Tensor(a!) dst, Tensor? idx, Tensor? theta_in, Tensor(b!)? theta_out, "
+        "Tensor? disp_in, Tensor(c!)? disp_out, Tensor gauss, int seed, int epoch, float max_shift, float max_rot_deg, "
+        "float max_scale, float alpha) -> ()");
   m.def("sgd_flat(Tensor(a!) p, Tensor g, Tensor(b!) buf, float lr, float momentum, float dampening, "
         "float weight_decay, bool nesterov, float grad_scale, Tensor(c!) step, Tensor(d!) ticket, "
         "Tensor? lr_table=None, Tensor(e!)? lr_pos=None) -> ()");
@@ -1261,6 +1305,7 @@ TORCH_LIBRARY(csed, m) {
 TORCH_LIBRARY_IMPL(csed, CUDA, m) {
   m.impl("gather_normalize", &gather_normalize);
   m.impl("augment_affine", &augment_affine);
+  m.impl("augment_elastic", &augment_elastic);
   m.impl("sgd_flat", &sgd_flat);
   m.impl("log_softmax_fwd", &log_softmax_fwd);
   m.impl("log_softmax_bwd", &log_softmax_bwd);

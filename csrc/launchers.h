@@ -32,6 +32,16 @@ hipError_t launch_augment_affine(const uint8_t* src, uint8_t* dst, const int64_t
                                  float* theta_out, int64_t N, int64_t M, uint64_t seed, uint64_t epoch,
                                  float max_shift, float max_rot_deg, float max_scale, hipStream_t s);
 
+// Elastic augmentation (kernels/augment_elastic.hip): augment_affine's rows, idx and theta semantics, with a
+// per-pixel displacement added to the sampling coordinate: disp_in[i] (float32 [2, 28, 28]: x then y
+// displacements) or, disp_in null, alpha (G U G) with U drawn from philox_uniform(seed, epoch, 2^40 + 1568 r + ..)
+// and gauss the float32 [32, 32] zero-padded Gaussian matrix G; disp_out[i] (optional) gets the field used.
+// disp_in, disp_out, gauss: 16-byte aligned.
+hipError_t launch_augment_elastic(const uint8_t* src, uint8_t* dst, const int64_t* idx, const float* theta_in,
+                                  float* theta_out, const float* disp_in, float* disp_out, const float* gauss,
+                                  int64_t N, int64_t M, uint64_t seed, uint64_t epoch, float max_shift,
+                                  float max_rot_deg, float max_scale, float alpha, hipStream_t s);
+
 // ----------------------------------------------------------- optimizer ----
 // SGD with momentum over a flat fp32 buffer (torch.optim.SGD semantics).
 // step[0] == 0 means "momentum buffer not yet initialised" (buf = g).

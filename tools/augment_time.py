@@ -2,7 +2,9 @@
 the kernel's time for the whole 60,000-row epoch order and for a 7,500-row shard (device events around back-to-back
 launches, so launch gaps are included: an upper bound), the fused engine's warm epoch time with and without
 --augment-shift 2 --augment-rotate 15 (two engines, alternating), and validation accuracy after 3 epochs with and
-without.  Prints one JSON line.  profiles/augment.md records a run."""
+without.  --elastic ALPHA SIGMA measures data.ElasticAugment (csrc/kernels/augment_elastic.hip) on top of the same
+affine maxima instead: its launches next to the affine kernel's in the same run, and "on" is the elastic augmenter.
+Prints one JSON line.  profiles/augment.md records a run."""
 from __future__ import annotations
 
 import argparse
@@ -15,7 +17,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from csed_514_project_distributed_training_using_pytorch_amd.data import AffineAugment, synthetic_mnist  # noqa: E402
+from csed_514_project_distributed_training_using_pytorch_amd.data import AffineAugment, ElasticAugment, synthetic_mnist  # noqa: E402
 from csed_514_project_distributed_training_using_pytorch_amd.engine.fused import FusedLeNetTrainer  # noqa: E402
 from csed_514_project_distributed_training_using_pytorch_amd.models import Net  # noqa: E402
 
@@ -45,17 +47,23 @@ def main() -> int:
     ap.add_argument("--train-size", type=int, default=60000)
     ap.add_argument("--test-size", type=int, default=10000)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--elastic", type=float, nargs=2, default=None, metavar=("ALPHA", "SIGMA"))
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     train, test = synthetic_mnist(args.train_size, seed=0), synthetic_mnist(args.test_size, seed=0, train=False)
     n = len(train)
-    make = lambda: AffineAugment(max_shift=2, max_rot_deg=15, seed=1)  # noqa: E731
+    affine = lambda: AffineAugment(max_shift=2, max_rot_deg=15, seed=1)  # noqa: E731
+    make = affine if args.elastic is None else lambda: ElasticAugment(*args.elastic, max_shift=2, max_rot_deg=15, seed=1)
     src = train.images.to(dev)
     dst = src.clone()
     gen = torch.Generator().manual_seed(0)
     order = torch.randperm(n, generator=gen).to(dev)
     rec = {"rows": n, "kernel_us": {str(m): kernel_us(make(), src, dst, order[:m].contiguous(), 50, args.rounds)
                                     for m in (n, n // 8)}}
+    if args.elastic is not None:  # the affine kernel's figure from the same run, to set the elastic one against
+        rec["elastic"] = args.elastic
+        rec["affine_kernel_us"] = {str(m): kernel_us(affine(), src, dst, order[:m].contiguous(), 50, args.rounds)
+                                   for m in (n, n // 8)}
     engs = {"off": engine(dev, train, None), "on": engine(dev, train, make())}
     epoch_ms = {"off": [], "on": []}
     for r in range(args.rounds + 1):  # (round 0 captures the graphs and warms up)
