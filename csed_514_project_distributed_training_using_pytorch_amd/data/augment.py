@@ -16,6 +16,10 @@ b = -cc = sin(phi) / s, e = -dx, f = -dy.
 
 ``ElasticAugment`` adds a per-row smoothed random displacement field to the sampling coordinate
 (``csed::augment_elastic``, csrc/kernels/augment_elastic.hip) behind the same interface.
+
+``StrokeAugment`` changes what no coordinate map can: stroke thickness (grey-level dilation / erosion by a disc) and
+occlusion (a random rectangle set to 0), in integer arithmetic (``csed::augment_stroke``,
+csrc/kernels/augment_stroke.hip).  It wraps one of the other two, or stands alone.
 """
 from __future__ import annotations
 
@@ -190,3 +194,137 @@ def _warp_cpu(img: torch.Tensor, theta: torch.Tensor, disp: torch.Tensor | None 
     v10, v11 = flat.gather(1, cell + 31), flat.gather(1, cell + 32)
     v = (1 - fy) * ((1 - fx) * v00 + fx * v01) + fy * ((1 - fx) * v10 + fx * v11)
     return (v + 0.5).floor().clamp_(max=255).to(torch.uint8)
+
+
+STROKE_STREAM = 1 << 41  # first Philox index of the stroke draws (the elastic fields end well below it)
+STROKE_SPANS = ((0,), (1, 0), (2, 1, 0), (3, 2, 2, 0))  # w_k(|dy|): the discs dx^2 + dy^2 <= k^2 as row half-widths
+
+
+class StrokeAugment:
+    """Stroke thickness and random erasing (docs/ARCHITECTURE.md "Stroke augmentation"), optionally after an
+    ``AffineAugment`` / ``ElasticAugment`` (``inner``): every row is dilated or eroded by a disc of a random signed
+    radius of up to ``max_thickness`` pixels (0 .. 3, in 1/256 px, two neighbouring integer discs blended), and with
+    probability ``erase_p`` a random rectangle with sides in ``erase_size`` = (lo, hi) is set to 0.  All of it is
+    integer arithmetic on the bytes: ``csed::augment_stroke`` (csrc/kernels/augment_stroke.hip) and the CPU path
+    agree bit for bit.  The parameters (q, e, top, left, h, w) of a row are a pure function of (seed, epoch, dataset
+    row); ``seed`` and ``epoch`` are shared with ``inner``.  With its own part off the augmenter is ``inner``, launch
+    for launch."""
+
+    CPU_CHUNK = 4096  # rows per pass of the CPU path
+
+    def __init__(self, max_thickness: float = 0.0, erase_p: float = 0.0, erase_size: tuple[int, int] = (4, 12),
+                 inner: AffineAugment | None = None, seed: int | None = None):
+        max_thickness, erase_p = float(max_thickness), float(erase_p)
+        lo, hi = (int(v) if float(v).is_integer() else -1 for v in map(float, erase_size))  # (NaN, 4.5: rejected)
+        if not (0 <= max_thickness <= 3 and 0 <= erase_p <= 1 and 1 <= lo <= hi <= 28):
+            raise ValueError(f"stroke augmentation thickness {max_thickness} px, erase probability {erase_p}, erase "
+                             f"size {tuple(erase_size)}: expected 0 <= thickness <= 3, 0 <= probability <= 1 and "
+                             f"integer sides 1 <= lo <= hi <= 28")
+        self.max_thickness, self.erase_p, self.erase_size, self.inner = max_thickness, erase_p, (lo, hi), inner
+        self._seed = None if seed is None else int(seed) & 0xFFFFFFFFFFFF
+        if inner is not None and seed is not None:
+            inner._seed = self._seed
+        self.epoch = 0 if inner is None else inner.epoch
+
+    @property
+    def seed(self) -> int:
+        if self._seed is None:  # inner's, which follows torch.manual_seed() as AffineAugment's does
+            self._seed = self.inner.seed if self.inner is not None else torch.initial_seed() & 0xFFFFFFFFFFFF
+        return self._seed
+
+    @property
+    def epoch(self) -> int:
+        return self._epoch
+
+    @epoch.setter
+    def epoch(self, value: int) -> None:  # (the engines do ``augment.epoch += 1``; inner draws at the same epoch)
+        self._epoch = value
+        if self.inner is not None:
+            self.inner.epoch = value
+
+    @property
+    def own(self) -> bool:
+        return self.max_thickness > 0 or self.erase_p > 0
+
+    @property
+    def enabled(self) -> bool:
+        return self.own or (self.inner is not None and self.inner.enabled)
+
+    def draw(self, rows: torch.Tensor) -> torch.Tensor:
+        """The int32 [M, 6] parameters (q, e, top, left, h, w) of dataset rows ``rows`` at the current epoch, on the
+        host: the kernel's own draw, value for value."""
+        import numpy as np
+
+        r = rows.detach().cpu().numpy().astype(np.uint64)
+        u = [philox_uniform_reference(self.seed, self.epoch, np.uint64(STROKE_STREAM) + np.uint64(8) * r + np.uint64(j))
+             .astype(np.float32) for j in range(6)]  # (multiples of 2^-24: exact in float32)
+        U = [(v.astype(np.float64) * 16777216.0).astype(np.int64) for v in u]
+        t = (np.float32(2) * u[0] - np.float32(1)) * np.float32(self.max_thickness)  # float32, one rounding
+        q = np.sign(t).astype(np.int64) * np.floor(np.abs(t) * np.float32(256)).astype(np.int64)
+        lo, hi = self.erase_size
+        n = hi - lo + 1
+        h, w = lo + ((U[2] * n) >> 24), lo + ((U[3] * n) >> 24)
+        cols = [q, u[1] < np.float32(self.erase_p), (U[4] * (29 - h)) >> 24, (U[5] * (29 - w)) >> 24, h, w]
+        return torch.from_numpy(np.stack([c.astype(np.int32) for c in cols], 1))
+
+    def apply(self, src: torch.Tensor, dst: torch.Tensor, idx: torch.Tensor | None = None,
+              params: torch.Tensor | None = None, return_params: bool = False) -> torch.Tensor | None:
+        """Rows ``idx`` (int64; None: all) of the uint8 set ``src`` into the same rows of ``dst``: first through
+        ``inner`` (if enabled), then thickened / thinned and erased by each row's parameters drawn at ``self.epoch``
+        -- or by ``params`` (int32 [M, 6], one entry per entry of ``idx``), a plain morphology + mask.
+        ``return_params``: the int32 parameters used.  ``dst`` may be ``src``; the entries of ``idx`` must then be
+        distinct (an epoch order's are), since a row named twice would be processed twice.  On a GPU this is one
+        launch of ``csed::augment_stroke`` (after inner's, in place on ``dst``); on the CPU the same definition in
+        integer torch ops (the plumbing path of ``--device cpu``)."""
+        inner = self.inner if self.inner is not None and self.inner.enabled else None
+        if inner is not None:
+            if not self.own and params is None and not return_params:
+                return inner.apply(src, dst, idx)
+            inner.apply(src, dst, idx)
+            src = dst
+        lo, hi = self.erase_size
+        if src.device.type == "cuda":
+            from ..ops import _native
+
+            M = src.shape[0] if idx is None else idx.numel()
+            out = torch.empty((M, 6), dtype=torch.int32, device=src.device) if return_params else None
+            _native.ops().augment_stroke(src, dst, idx, params, out, self.seed, self.epoch, self.max_thickness,
+                                         self.erase_p, lo, hi)
+            return out
+        rows = torch.arange(src.shape[0]) if idx is None else idx.to(torch.long)
+        params = self.draw(rows) if params is None else params.to(torch.int32).clone()
+        params[:, 0].clamp_(-768, 768)
+        for s in range(0, rows.numel(), self.CPU_CHUNK):
+            c = rows[s:s + self.CPU_CHUNK]
+            dst.view(-1, 784)[c] = _stroke_cpu(src.view(-1, 784)[c], params[s:s + self.CPU_CHUNK])
+        return params if return_params else None
+
+
+def _stroke_cpu(img: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
+    """uint8 [M, 784] through the stroke definition with int32 [M, 6] parameters (q already clamped).  Erosion runs
+    as dilation of the complemented image inside a border of 255, i.e. of zeros before the complement."""
+    M = img.shape[0]
+    P = params.to(torch.int64).view(M, 6, 1, 1)
+    q, e, top, left, h, w = (P[:, j] for j in range(6))
+    a, neg = q.abs(), q < 0
+    k, p = a >> 8, a & 255
+    k1 = (k + 1).clamp(max=3)
+    I = img.view(M, 28, 28).to(torch.int64)
+    I = torch.where(neg, 255 - I, I)
+    pad = (neg * 255).expand(M, 34, 34).clone()
+    pad[:, 3:31, 3:31] = I
+    maxima = [I]  # M_0 .. M_3: shifted maxima over the discs' spans
+    for spans in STROKE_SPANS[1:]:
+        m = I
+        for ady, half in enumerate(spans):
+            for dy in {ady, -ady}:
+                for dx in range(-half, half + 1):
+                    m = torch.maximum(m, pad[:, 3 + dy:31 + dy, 3 + dx:31 + dx])
+        maxima.append(m)
+    S = torch.stack(maxima, 1)
+    S = torch.where(neg.view(M, 1, 1, 1), 255 - S, S)
+    at = torch.arange(M)
+    v = (S[at, k.view(M)] * (256 - p) + S[at, k1.view(M)] * p + 128) >> 8
+    y, x = torch.arange(28).view(1, 28, 1), torch.arange(28).view(1, 1, 28)
+    erased = (e != 0) & (y >= top) & (y < top + h) & (x >= left) & (x < left + w)
+    return v.masked_fill(erased, 0).to(torch.uint8).view(M, 784)

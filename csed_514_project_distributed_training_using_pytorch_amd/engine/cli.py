@@ -24,7 +24,7 @@ import time
 import torch
 
 from .. import ops
-from ..data import AffineAugment, DeviceLoader, ElasticAugment, get_mnist
+from ..data import AffineAugment, DeviceLoader, ElasticAugment, StrokeAugment, get_mnist
 from ..models import Net
 from ..parallel.comm import all_reduce_max, barrier, destroy, init_distributed, replica_checksum
 from ..parallel.sampler import ShardSampler
@@ -74,11 +74,19 @@ def _common_flags(ap: argparse.ArgumentParser) -> None:
                          "affine flags (data.ElasticAugment; try 34 with sigma 4)")
     ap.add_argument("--augment-elastic-sigma", type=float, default=4.0, metavar="SIGMA",
                     help="the Gaussian's standard deviation in pixels (default 4.0)")
+    ap.add_argument("--augment-thickness", type=float, default=0.0, metavar="PX",
+                    help="random stroke thickening / thinning of every training digit by up to PX pixels (0 .. 3), "
+                         "after the flags above (data.StrokeAugment: one more kernel per epoch, in place)")
+    ap.add_argument("--augment-erase", type=float, default=0.0, metavar="P",
+                    help="random erasing: with probability P a random rectangle of the digit is set to 0")
+    ap.add_argument("--augment-erase-size", type=int, nargs=2, default=[4, 12], metavar=("LO", "HI"),
+                    help="the erased rectangle's sides are drawn from LO .. HI pixels (default 4 12)")
 
 
 def _make_augment(args):
-    """The --augment-* flags as a data.AffineAugment (data.ElasticAugment under --augment-elastic) seeded by
-    --seed, or None when nothing is switched on."""
+    """The --augment-* flags as a data.AffineAugment (data.ElasticAugment under --augment-elastic), inside a
+    data.StrokeAugment under --augment-thickness / --augment-erase, seeded by --seed, or None when nothing is
+    switched on."""
     affine = (args.augment_shift, args.augment_rotate, args.augment_scale)
     try:
         if args.augment_elastic != 0 or args.augment_elastic_sigma != 4.0:
@@ -88,6 +96,12 @@ def _make_augment(args):
     except ValueError as e:
         raise SystemExit(f"--augment-shift / --augment-rotate / --augment-scale / --augment-elastic / "
                          f"--augment-elastic-sigma: {e}")
+    if args.augment_thickness != 0 or args.augment_erase != 0:
+        try:
+            aug = StrokeAugment(args.augment_thickness, args.augment_erase, tuple(args.augment_erase_size), inner=aug,
+                                seed=args.seed)
+        except ValueError as e:
+            raise SystemExit(f"--augment-thickness / --augment-erase / --augment-erase-size: {e}")
     return aug if aug.enabled else None
 
 

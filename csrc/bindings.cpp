@@ -85,17 +85,17 @@ void gather_normalize(const Tensor& src, const Tensor& idx, const optional<Tenso
                                           cur_stream(src)));
 }
 
-// The argument checks both augmentation ops share; returns M, the number of rows the launch names.
-int64_t check_augment(const char* op, const Tensor& src, const Tensor& dst, const optional<Tensor>& idx,
-                      const optional<Tensor>& theta_in, const optional<Tensor>& theta_out, int64_t seed,
-                      int64_t epoch, double max_shift, double max_rot_deg, double max_scale) {
+// The row checks every augmentation op shares; returns M, the number of rows the launch names.  in_place: dst
+// may be src itself (any other overlap stays an error).
+int64_t check_augment_rows(const char* op, const Tensor& src, const Tensor& dst, const optional<Tensor>& idx,
+                           int64_t seed, int64_t epoch, bool in_place) {
   dev(src, "src"); dev(dst, "dst");
   TORCH_CHECK(src.scalar_type() == at::kByte && dst.scalar_type() == at::kByte, op, ": src and dst are uint8");
   TORCH_CHECK(src.sizes() == dst.sizes() && src.device() == dst.device(), op, ": src and dst differ in shape or device");
   TORCH_CHECK(src.dim() >= 2 && src.numel() == src.size(0) * 784, op, ": rows of 784 bytes ([N, 784] or [N, 28, 28])");
   const auto* s0 = src.data_ptr<uint8_t>();
   const auto* d0 = dst.data_ptr<uint8_t>();
-  TORCH_CHECK(s0 + src.numel() <= d0 || d0 + dst.numel() <= s0, op, ": src and dst overlap");
+  TORCH_CHECK((in_place && s0 == d0) || s0 + src.numel() <= d0 || d0 + dst.numel() <= s0, op, ": src and dst overlap");
   TORCH_CHECK(((uintptr_t)s0 | (uintptr_t)d0) % 16 == 0, op, ": src and dst must be 16-byte aligned");
   int64_t M = src.size(0);
   if (idx.has_value()) {
@@ -104,13 +104,25 @@ int64_t check_augment(const char* op, const Tensor& src, const Tensor& dst, cons
     M = idx->numel();
   }
   TORCH_CHECK(M < (int64_t(1) << 31), op, ": too many rows");
-  for (const auto* t : {&theta_in, &theta_out}) {
-    if (!t->has_value()) continue;
-    dev(**t, "theta");
-    TORCH_CHECK((*t)->scalar_type() == at::kFloat && (*t)->dim() == 2 && (*t)->size(0) == M && (*t)->size(1) == 6,
-                op, ": theta_in / theta_out are float32 [M, 6] with M = ", M);
-  }
   TORCH_CHECK(seed >= 0 && epoch >= 0, op, ": seed and epoch are >= 0");
+  return M;
+}
+
+// An optional [M, 6] per-row parameter tensor of an augmentation op (theta_in / theta_out, params_in / params_out).
+void check_augment_params(const char* op, const char* what, const optional<Tensor>& t, at::ScalarType type, int64_t M) {
+  if (!t.has_value()) return;
+  dev(*t, what);
+  TORCH_CHECK(t->scalar_type() == type && t->dim() == 2 && t->size(0) == M && t->size(1) == 6,
+              op, ": ", what, " is ", c10::toString(type), " [M, 6] with M = ", M);
+}
+
+// The argument checks the two warping ops share.
+int64_t check_augment(const char* op, const Tensor& src, const Tensor& dst, const optional<Tensor>& idx,
+                      const optional<Tensor>& theta_in, const optional<Tensor>& theta_out, int64_t seed,
+                      int64_t epoch, double max_shift, double max_rot_deg, double max_scale) {
+  const int64_t M = check_augment_rows(op, src, dst, idx, seed, epoch, /*in_place=*/false);
+  check_augment_params(op, "theta_in", theta_in, at::kFloat, M);
+  check_augment_params(op, "theta_out", theta_out, at::kFloat, M);
   TORCH_CHECK(max_shift >= 0 && max_rot_deg >= 0 && max_scale >= 0 && max_scale < 1,
               op, ": expected max_shift >= 0, max_rot_deg >= 0 and 0 <= max_scale < 1");
   return M;
@@ -161,6 +173,25 @@ void augment_elastic(const Tensor& src, Tensor& dst, const optional<Tensor>& idx
                                          optpt<float>(disp_out), gauss.data_ptr<float>(), src.size(0), M,
                                          (uint64_t)seed, (uint64_t)epoch, (float)max_shift, (float)max_rot_deg,
                                          (float)max_scale, (float)alpha, cur_stream(src)));
+}
+
+// Stroke-thickness and random-erasing augmentation, kernels/augment_stroke.hip: augment_affine's rows and idx;
+// params_in (int32 [M, 6]: q, e, top, left, h, w) replaces the draw, params_out gets the values used.  dst may be
+// src; the entries of idx must then be distinct (a row named twice would be processed twice, in no fixed order).
+void augment_stroke(const Tensor& src, Tensor& dst, const optional<Tensor>& idx, const optional<Tensor>& params_in,
+                    const optional<Tensor>& params_out, int64_t seed, int64_t epoch, double max_thickness,
+                    double erase_p, int64_t erase_lo, int64_t erase_hi) {
+  const int64_t M = check_augment_rows("augment_stroke", src, dst, idx, seed, epoch, /*in_place=*/true);
+  check_augment_params("augment_stroke", "params_in", params_in, at::kInt, M);
+  check_augment_params("augment_stroke", "params_out", params_out, at::kInt, M);
+  TORCH_CHECK(max_thickness >= 0 && max_thickness <= 3 && erase_p >= 0 && erase_p <= 1 && 1 <= erase_lo &&
+                  erase_lo <= erase_hi && erase_hi <= 28,
+              "augment_stroke: expected 0 <= max_thickness <= 3, 0 <= erase_p <= 1 and 1 <= erase_lo <= erase_hi <= 28");
+  const c10::DeviceGuard g(src.device());
+  CHECK_HIP(csed::launch_augment_stroke(src.data_ptr<uint8_t>(), dst.data_ptr<uint8_t>(), optpt<int64_t>(idx),
+                                        optpt<int>(params_in), optpt<int>(params_out), src.size(0), M,
+                                        (uint64_t)seed, (uint64_t)epoch, (float)max_thickness, (float)erase_p,
+                                        (int)erase_lo, (int)erase_hi, cur_stream(src)));
 }
 
 // ------------------------------------------------------------- optimizer
@@ -1255,6 +1286,8 @@ TORCH_LIBRARY(csed, m) {
   m.def("augment_elastic(Tensor src, Tensor(a!) dst, Tensor? idx, Tensor? theta_in, Tensor(b!)? theta_out, "
         "Tensor? disp_in, Tensor(c!)? disp_out, Tensor gauss, int seed, int epoch, float max_shift, float max_rot_deg, "
         "float max_scale, float alpha) -> ()");
+  m.def("augment_stroke(Tensor src, Tensor(a!) dst, Tensor? idx, Tensor? params_in, Tensor(b!)? params_out, int seed, "
+        "int epoch, float max_thickness, float erase_p, int erase_lo, int erase_hi) -> ()");
   m.def("sgd_flat(Tensor(a!) p, Tensor g, Tensor(b!) buf, float lr, float momentum, float dampening, "
         "float weight_decay, bool nesterov, float grad_scale, Tensor(c!) step, Tensor(d!) ticket, "
         "Tensor? lr_table=None, Tensor(e!)? lr_pos=None) -> ()");
@@ -1306,6 +1339,7 @@ TORCH_LIBRARY_IMPL(csed, CUDA, m) {
   m.impl("gather_normalize", &gather_normalize);
   m.impl("augment_affine", &augment_affine);
   m.impl("augment_elastic", &augment_elastic);
+  m.impl("augment_stroke", &augment_stroke);
   m.impl("sgd_flat", &sgd_flat);
   m.impl("log_softmax_fwd", &log_softmax_fwd);
   m.impl("log_softmax_bwd", &log_softmax_bwd);

@@ -42,6 +42,16 @@ hipError_t launch_augment_elastic(const uint8_t* src, uint8_t* dst, const int64_
                                   int64_t N, int64_t M, uint64_t seed, uint64_t epoch, float max_shift,
                                   float max_rot_deg, float max_scale, float alpha, hipStream_t s);
 
+// Stroke-thickness and random-erasing augmentation (kernels/augment_stroke.hip): row r = idx[i] (idx null:
+// r = i), i < M, of the uint8 [N, 784] set src is dilated / eroded by a disc of signed radius q / 256 px and
+// then cleared inside a rectangle, by params_in[i] (six ints: q, e, top, left, h, w) or, params_in null, by the
+// parameters drawn from philox_uniform(seed, epoch, 2^41 + 8 r + 0..5); params_out[i] (optional) gets the values
+// used (q clamped to [-768, 768]).  A row whose index is outside [0, N) is skipped.  src, dst: 16-byte aligned;
+// dst may be src (the entries of idx distinct).  1 <= erase_lo <= erase_hi <= 28.
+hipError_t launch_augment_stroke(const uint8_t* src, uint8_t* dst, const int64_t* idx, const int* params_in,
+                                 int* params_out, int64_t N, int64_t M, uint64_t seed, uint64_t epoch,
+                                 float max_thickness, float erase_p, int erase_lo, int erase_hi, hipStream_t s);
+
 // ----------------------------------------------------------- optimizer ----
 // SGD with momentum over a flat fp32 buffer (torch.optim.SGD semantics).
 // step[0] == 0 means "momentum buffer not yet initialised" (buf = g).

@@ -4,6 +4,8 @@ launches, so launch gaps are included: an upper bound), the fused engine's warm 
 --augment-shift 2 --augment-rotate 15 (two engines, alternating), and validation accuracy after 3 epochs with and
 without.  --elastic ALPHA SIGMA measures data.ElasticAugment (csrc/kernels/augment_elastic.hip) on top of the same
 affine maxima instead: its launches next to the affine kernel's in the same run, and "on" is the elastic augmenter.
+--stroke T P measures data.StrokeAugment (csrc/kernels/augment_stroke.hip): its own launch next to the affine
+kernel's, and "on" is the stroke augmenter alone or, under --shift PX, around an AffineAugment of that shift.
 Prints one JSON line.  profiles/augment.md records a run."""
 from __future__ import annotations
 
@@ -17,7 +19,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from csed_514_project_distributed_training_using_pytorch_amd.data import AffineAugment, ElasticAugment, synthetic_mnist  # noqa: E402
+from csed_514_project_distributed_training_using_pytorch_amd.data import AffineAugment, ElasticAugment, StrokeAugment, synthetic_mnist  # noqa: E402
 from csed_514_project_distributed_training_using_pytorch_amd.engine.fused import FusedLeNetTrainer  # noqa: E402
 from csed_514_project_distributed_training_using_pytorch_amd.models import Net  # noqa: E402
 
@@ -48,20 +50,27 @@ def main() -> int:
     ap.add_argument("--test-size", type=int, default=10000)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--elastic", type=float, nargs=2, default=None, metavar=("ALPHA", "SIGMA"))
+    ap.add_argument("--stroke", type=float, nargs=2, default=None, metavar=("T", "P"))
+    ap.add_argument("--erase-size", type=int, nargs=2, default=[4, 12], metavar=("LO", "HI"))
+    ap.add_argument("--shift", type=float, default=0.0, metavar="PX", help="with --stroke: the inner augmenter's shift")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     train, test = synthetic_mnist(args.train_size, seed=0), synthetic_mnist(args.test_size, seed=0, train=False)
     n = len(train)
     affine = lambda: AffineAugment(max_shift=2, max_rot_deg=15, seed=1)  # noqa: E731
     make = affine if args.elastic is None else lambda: ElasticAugment(*args.elastic, max_shift=2, max_rot_deg=15, seed=1)
+    stroke = None
+    if args.stroke is not None:  # the stroke kernel alone is what is timed; "on" may wrap an affine augmenter
+        stroke = lambda inner=None: StrokeAugment(*args.stroke, tuple(args.erase_size), inner=inner, seed=1)  # noqa: E731
+        make = lambda: stroke(AffineAugment(max_shift=args.shift, seed=1) if args.shift else None)  # noqa: E731
     src = train.images.to(dev)
     dst = src.clone()
     gen = torch.Generator().manual_seed(0)
     order = torch.randperm(n, generator=gen).to(dev)
-    rec = {"rows": n, "kernel_us": {str(m): kernel_us(make(), src, dst, order[:m].contiguous(), 50, args.rounds)
+    rec = {"rows": n, "kernel_us": {str(m): kernel_us((stroke or make)(), src, dst, order[:m].contiguous(), 50, args.rounds)
                                     for m in (n, n // 8)}}
-    if args.elastic is not None:  # the affine kernel's figure from the same run, to set the elastic one against
-        rec["elastic"] = args.elastic
+    if args.elastic is not None or stroke is not None:  # the affine kernel's figure from the same run, to set it against
+        rec.update({"elastic": args.elastic} if stroke is None else {"stroke": args.stroke, "shift": args.shift})
         rec["affine_kernel_us"] = {str(m): kernel_us(affine(), src, dst, order[:m].contiguous(), 50, args.rounds)
                                    for m in (n, n // 8)}
     engs = {"off": engine(dev, train, None), "on": engine(dev, train, make())}
