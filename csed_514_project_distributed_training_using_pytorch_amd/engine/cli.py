@@ -61,6 +61,12 @@ def _common_flags(ap: argparse.ArgumentParser) -> None:
                          "optimizer step (on the device, inside the update kernel): one more line with its loss "
                          "and accuracy after each validation line, and results/ema.pth next to results/model.pth "
                          "(default: off)")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
+                    help="clip every step's gradient to the global 2-norm X before the update "
+                         "(torch.nn.utils.clip_grad_norm_'s rule: g *= min(1, X / (norm + 1e-6))): on a GPU one HIP "
+                         "kernel on the flat gradient in either engine (data-parallel ranks of the fused engine then "
+                         "exchange through the process-group all-reduce), with --device cpu torch's own function "
+                         "(default: off)")
     ap.add_argument("--augment-shift", type=float, default=0.0, metavar="PX",
                     help="random shift of every training digit by up to PX pixels in x and y, drawn anew each "
                          "epoch (data.AffineAugment: one kernel per epoch writes the augmented train set)")
@@ -147,7 +153,7 @@ def _modular_adam(args, tr, net) -> None:
     cls = torch.optim.AdamW if args.optimizer == "adamw" else torch.optim.Adam
     tr.opt = cls(net.parameters(), lr=args.lr, betas=(args.beta1, args.beta2), eps=args.eps,
                  weight_decay=args.weight_decay)
-    tr.opt.on_gpu = False
+    tr.opt.on_gpu = False  # (--clip-grad-norm: the trainer clips with torch's function in front of this optimizer)
 
 
 def _check_resume_optimizer(args, path: str) -> None:
@@ -175,6 +181,8 @@ def _make_schedule(args, steps_per_epoch: int):
 
 
 def _check_ema_flag(args) -> None:
+    if args.clip_grad_norm is not None and not args.clip_grad_norm > 0.0:
+        raise SystemExit(f"--clip-grad-norm {args.clip_grad_norm}: expected a positive value")
     if args.ema_decay is not None and not 0.0 <= args.ema_decay < 1.0:
         raise SystemExit(f"--ema-decay {args.ema_decay}: expected 0 <= D < 1")
 
@@ -293,6 +301,7 @@ def single_main(argv=None) -> int:
             if saved is not None:
                 eng.load_ema_state_dict(saved)
         eng.set_augment(aug)
+        eng.set_grad_clip(args.clip_grad_norm)
 
         def test():
             lsum, correct = eng.evaluate(test_set)
@@ -358,7 +367,8 @@ def single_main(argv=None) -> int:
     else:
         from .modular import ModularTrainer
 
-        tr = ModularTrainer(net, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
+        tr = ModularTrainer(net, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
+                            max_grad_norm=args.clip_grad_norm)
         _modular_adam(args, tr, net)
         if args.resume:
             checkpoint.load_checkpoint(net, tr.opt, os.path.join(results, "model.pth"),
@@ -506,6 +516,7 @@ def dist_main(argv=None) -> int:
             eng.set_ema(args.ema_decay)
         ema_sd = eng.ema_state_dict if args.ema_decay is not None else None
         eng.set_augment(aug)
+        eng.set_grad_clip(args.clip_grad_norm)
         sampler.set_epoch(0)
         order = sampler.indices()
         i = 0
@@ -587,7 +598,7 @@ def dist_main(argv=None) -> int:
 
         tr = ModularTrainer(net, lr=args.lr, momentum=args.momentum, ctx=ctx, loss="ce",
                             bucket_cap_mb=25.0 if args.bucket_mb is None else args.bucket_mb,
-                            weight_decay=args.weight_decay)
+                            weight_decay=args.weight_decay, max_grad_norm=args.clip_grad_norm)
         _modular_adam(args, tr, net)
         loader = DeviceLoader(train, per_rank, sampler=sampler, device=dev,
                               dtype=ops.compute_dtype() if dev.type == "cuda" else torch.float32, augment=aug)

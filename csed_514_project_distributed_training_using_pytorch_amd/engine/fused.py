@@ -296,6 +296,8 @@ class FusedLeNetTrainer:
         self.ema: torch.Tensor | None = None  # the parameters' moving average (set_ema), or None: off
         self.ema_decay = 0.0
         self._ema_wimg: torch.Tensor | None = None  # its weight image, packed for evaluate(ema=True)
+        self.max_grad_norm: float | None = None  # set_grad_clip: the gradient's 2-norm is clipped to it, or None: off
+        self.clip_stats: torch.Tensor | None = None  # fp32 [2] (norm before the clip, coefficient) of the last step
         self.augment = None  # data.AffineAugment (set_augment), or None: the training launches read train_data.images
         self._aug_images: torch.Tensor | None = None  # the epoch's augmented copy of train_data.images
         self.native_max = native_max_steps()
@@ -390,9 +392,9 @@ class FusedLeNetTrainer:
             return f"fused-ipc-loopback{self.loopback_world}"
         if not self.comm:
             return "none"
-        if self.exch is not None:
+        if self.exch is not None and self.max_grad_norm is None:
             return "fused-ipc"
-        return "rccl"
+        return "rccl"  # (also under a gradient clip: the clip sits between the reduce and the apply launch)
 
     # ------------------------------------------------- fused gradient exchange
     def select_path(self) -> bool:
@@ -632,6 +634,16 @@ class FusedLeNetTrainer:
         the full step's.  What _launch_step runs and what graph() keys on (replay.launch_key)."""
         # full steps read the staged batch and stage the next one; the epoch's short tail uses perm
         train = ("lenet_train", self.train_args(perm=perm, stage_next=True, **kw))
+        if self.max_grad_norm is not None:
+            # the split update with the clip (csrc/kernels/clip.hip) between its launches: g is the mean-loss
+            # gradient (the reduce launch applies the 16-bit steps' grad_post), summed over the ranks by the process
+            # group -- the in-kernel exchange belongs to the one-kernel "step" form -- so every rank clips the same
+            # gradient by the same coefficient
+            g = self.flat.grad
+            return ([train, self.update_launch("reduce", grad=g, exchange=False, **kw)]
+                    + ([("all_reduce", (g,))] if self.comm else [])
+                    + [("clip_grad_norm_", (g, self.max_grad_norm, self.clip_stats, None)),
+                       self.update_launch("apply", grad=g, **kw)])
         if self.exch is not None or not self.comm:  # one kernel: the fused exchange, or no exchange at all
             return [train, self.update_launch("step", **kw)]
         g = self.flat.grad
@@ -727,6 +739,8 @@ class FusedLeNetTrainer:
         if self._cap_stream is None:  # (one capture stream per engine: creating a stream costs ms)
             self._cap_stream = torch.cuda.Stream(self.device)
         kind = f"{'tail' if tail else 'full'}/{self.allreduce_kind}/{self.train_kernel}"
+        if self.max_grad_norm is not None:  # (other launches: the split update and the clip kernel warm up too)
+            kind += "/clip"
         self._stamp("capture.stream", time.perf_counter() - t0)
         g = _replay.capture(self._tail_step if tail else self.step, nsteps, self._cap_stream,
                             None if kind in self._warmed else self._state(), self._stamp)
@@ -773,8 +787,8 @@ class FusedLeNetTrainer:
     def stepper(self):
         """The native step executor (``csrc/bindings.cpp:LenetStepper``) for this engine's full
         steps: both kernels' argument blocks built once, ``run(k)`` enqueues 2k launches from
-        C++.  None where a step is more than two launches (the all-reduce fallback)."""
-        if self.comm and self.exch is None:
+        C++.  None where a step is more than two launches (the all-reduce fallback, a gradient clip)."""
+        if (self.comm and self.exch is None) or self.max_grad_norm is not None:
             return None
         # (the split-K fc scratch also next to the exchange, where the launcher does not use it)
         train, (name, update) = self.train_args(stage_next=True), self.update_launch("step", fc_split=True)
@@ -952,6 +966,30 @@ class FusedLeNetTrainer:
         blocks hold the old rate or table: dropped, as in load_optimizer_state_dict."""
         self.lr_schedule = None if schedule is None else schedule.to(self.device)
         self.invalidate()
+
+    def set_grad_clip(self, max_norm: float | None) -> None:
+        """Clip every step's gradient to the 2-norm ``max_norm`` before it is applied (torch's
+        ``clip_grad_norm_``: g *= min(1, max_norm / (norm + 1e-6)), csrc/kernels/clip.hip); None switches it off.
+        A clipped step is the split update with the clip between its launches, train -> reduce (-> all-reduce)
+        -> clip -> apply: data-parallel ranks then exchange through the process group's all-reduce, not inside
+        the update kernel.  ``clip_stats`` holds the last step's (norm, coefficient) on the device.  The step's
+        launches change, so graphs are captured anew under their own keys."""
+        if max_norm is not None and not float(max_norm) > 0.0:
+            raise ValueError(f"max_norm {max_norm}: expected a positive value (None switches clipping off)")
+        if max_norm is not None and self.loopback_world:
+            raise ValueError("a gradient clip does not combine with the loopback exchange (a one-kernel step)")
+        self.max_grad_norm = None if max_norm is None else float(max_norm)
+        if self.max_grad_norm is not None and self.clip_stats is None:
+            self.clip_stats = _native.zeros(2, torch.float32, self.device)
+        if self.max_grad_norm is not None and self.comm and self.exch is not None:
+            self.exchange_note = (f"{self.exchange_note}; gradient clip set: steps exchange through the process-group "
+                                  "all-reduce (the in-kernel exchange belongs to the one-kernel step)")
+
+    def last_grad_norm(self) -> float:
+        """The gradient's norm before the last step's clip (one device read, only when called)."""
+        if self.clip_stats is None:
+            raise RuntimeError("no gradient clip is set (set_grad_clip)")
+        return float(self.clip_stats[0].item())
 
     def set_ema(self, decay: float | None) -> None:
         """Keep an exponential moving average of the parameters, ``e <- e + (1 - decay) * (p_new - e)`` in

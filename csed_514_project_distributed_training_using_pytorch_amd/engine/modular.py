@@ -40,7 +40,8 @@ from ..parallel.ddp import DistributedDataParallel
 class ModularTrainer:
     def __init__(self, model: torch.nn.Module, lr: float, momentum: float, ctx=None, loss: str = "nll",
                  bucket_cap_mb: float = 25.0, dampening: float = 0.0, weight_decay: float = 0.0,
-                 nesterov: bool = False, graph: bool = True, overlap: bool = True):
+                 nesterov: bool = False, graph: bool = True, overlap: bool = True,
+                 max_grad_norm: float | None = None):
         self.ctx = ctx
         self.model = model
         self.distributed = ctx is not None and ctx.is_distributed
@@ -48,14 +49,19 @@ class ModularTrainer:
         if self.distributed:
             self.ddp = DistributedDataParallel(model, bucket_cap_mb=bucket_cap_mb, overlap=overlap)
             self.opt = FusedSGD(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
-                                nesterov=nesterov, flat=self.ddp.flat)
+                                nesterov=nesterov, flat=self.ddp.flat, max_grad_norm=max_grad_norm)
             self.forward = self.ddp
         else:
             self.ddp = None
             self.opt = FusedSGD(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
-                                nesterov=nesterov)
+                                nesterov=nesterov, max_grad_norm=max_grad_norm)
             self.forward = model
         self.flat = self.opt.flat
+        # the gradient clip (global 2-norm): FusedSGD's own, right before its update -- after the reducer's
+        # finalize has joined and averaged every bucket; an optimizer swapped in for it (the CLI's torch Adam
+        # on the CPU) gets torch's clip_grad_norm_ from _step
+        self.max_grad_norm = self.opt.max_grad_norm
+        self._last_norm: float | None = None
         if self.opt.on_gpu:
             ops.rng.default_state.device_step = self.opt.step_count  # graph-replay-safe dropout masks
             for i, p in enumerate(self.flat.params):  # backward kernels write into the flat gradient
@@ -95,6 +101,8 @@ class ModularTrainer:
         if self._one is None or self._one.device != loss.device:
             self._one = torch.ones((), device=loss.device, dtype=loss.dtype)
         loss.backward(self._one)  # (a kept d loss / d loss: no fill kernel per step)
+        if self.max_grad_norm is not None and not isinstance(self.opt, FusedSGD):
+            self._last_norm = float(torch.nn.utils.clip_grad_norm_(self.flat.params, self.max_grad_norm))
         self.opt.step()
         return loss.detach()
 
@@ -130,7 +138,15 @@ class ModularTrainer:
         sch = self.opt.lr_schedule
         lr = float(g["lr"]) if sch is None else ("schedule", id(sch), sch.table.data_ptr(), sch.pos.data_ptr())
         return (lr, float(g["momentum"]), float(g["dampening"]), float(g["weight_decay"]),
-                bool(g["nesterov"]), float(self.opt.grad_scale))
+                bool(g["nesterov"]), float(self.opt.grad_scale), self.opt.max_grad_norm)
+
+    def last_grad_norm(self) -> float:
+        """The gradient's norm before the last step's clip (GPU: one device read, only when called)."""
+        if isinstance(self.opt, FusedSGD):
+            return self.opt.last_grad_norm()
+        if self._last_norm is None:
+            raise RuntimeError("no gradient clip is set (max_grad_norm)")
+        return self._last_norm
 
     def _graph_key(self, x: torch.Tensor, target: torch.Tensor) -> tuple:
         return (tuple(x.shape), x.dtype, tuple(target.shape), self._hyper())

@@ -18,12 +18,14 @@ import math
 import torch
 
 from ..utils.flat import FlatParams
+from .clip import check_max_norm
 from .schedule import LRSchedule
 
 
 class FusedAdam(torch.optim.Adam):
     def __init__(self, params, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, decoupled: bool = False, flat: FlatParams | None = None):
+                 weight_decay: float = 0.0, decoupled: bool = False, flat: FlatParams | None = None,
+                 max_grad_norm: float | None = None):
         params = list(params)
         if any(isinstance(p, torch.Tensor) and p.device.type != "cpu" for p in params):  # (before anything is re-homed)
             raise NotImplementedError("FusedAdam steps CPU parameters only: the per-op engine has no flat Adam "
@@ -42,6 +44,16 @@ class FusedAdam(torch.optim.Adam):
         self.step_count = torch.zeros(1, dtype=torch.long, device=dev)  # steps taken: the next one is t = count + 1
         self.grad_scale = 1.0
         self.lr_schedule: LRSchedule | None = None
+        # clip the whole gradient to this 2-norm before every update (torch.nn.utils.clip_grad_norm_ on these
+        # CPU parameters; the GPU kernel, csed::clip_grad_norm_, runs in FusedSGD and the fused engine); None: off
+        self.max_grad_norm = check_max_norm(max_grad_norm)
+        self._last_norm: float | None = None
+
+    def last_grad_norm(self) -> float:
+        """The gradient's norm before the last step's clip."""
+        if self.max_grad_norm is None:
+            raise RuntimeError("no gradient clip is set (max_grad_norm)")
+        return float(self._last_norm)
 
     @property
     def decoupled(self) -> bool:
@@ -68,6 +80,10 @@ class FusedAdam(torch.optim.Adam):
                 loss = closure()
         g = self.param_groups[0]
         self.flat.gather_grads()
+        if self.max_grad_norm is not None:
+            if self.grad_scale != 1.0:
+                raise ValueError("max_grad_norm with grad_scale != 1: the clip acts on the unscaled flat gradient")
+            self._last_norm = float(torch.nn.utils.clip_grad_norm_(self.flat.params, self.max_grad_norm))
         self._cpu_step(g)
         return loss
 

@@ -17,12 +17,14 @@ import torch
 
 from ..ops import _native
 from ..utils.flat import FlatParams
+from .clip import GradClip, check_max_norm
 from .schedule import LRSchedule
 
 
 class FusedSGD(torch.optim.SGD):
     def __init__(self, params, lr: float = 0.01, momentum: float = 0.0, dampening: float = 0.0,
-                 weight_decay: float = 0.0, nesterov: bool = False, flat: FlatParams | None = None):
+                 weight_decay: float = 0.0, nesterov: bool = False, flat: FlatParams | None = None,
+                 max_grad_norm: float | None = None):
         params = list(params)
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                          nesterov=nesterov)
@@ -41,6 +43,36 @@ class FusedSGD(torch.optim.SGD):
         self.lr_schedule: LRSchedule | None = None
         self.ema_flat: torch.Tensor | None = None  # the parameters' moving average (set_ema), or None: off
         self.ema_decay = 0.0
+        self.max_grad_norm: float | None = None
+        self._clip: GradClip | None = None  # the device clip of flat.grad (GPU parameters)
+        self._last_norm: float | None = None  # CPU parameters: what torch's clip returned
+        self.set_grad_clip(max_grad_norm)
+
+    def set_grad_clip(self, max_norm: float | None) -> None:
+        """Clip the whole gradient to the 2-norm ``max_norm`` before every update (torch's
+        ``clip_grad_norm_``: g *= min(1, max_norm / (norm + 1e-6))); None switches it off.  On the GPU one more
+        launch on the flat gradient right before csed::sgd_flat (csrc/kernels/clip.hip) -- under the data-parallel
+        reducer that is after every bucket's all-reduce has been joined and averaged, so every rank clips the
+        same gradient by the same coefficient; on CPU parameters torch's own function."""
+        self.max_grad_norm = check_max_norm(max_norm)
+        on = self.max_grad_norm is not None and self.on_gpu
+        self._clip = GradClip(self.flat.grad[:self.flat.numel], self.max_grad_norm) if on else None
+
+    def last_grad_norm(self) -> float:
+        """The gradient's norm before the last step's clip (GPU: one device read, only when called)."""
+        if self.max_grad_norm is None:
+            raise RuntimeError("no gradient clip is set (max_grad_norm / set_grad_clip)")
+        return self._clip.last_norm() if self._clip is not None else float(self._last_norm)
+
+    def _clip_grads(self) -> None:
+        """The clip of a step, on the gathered flat gradient (grad_scale multiplies the gradient inside the
+        update, after the point where the clip would have to see it: the two do not combine)."""
+        if self.grad_scale != 1.0:
+            raise ValueError("max_grad_norm with grad_scale != 1: the clip acts on the unscaled flat gradient")
+        if self._clip is not None:
+            self._clip.launch()
+        else:
+            self._last_norm = float(torch.nn.utils.clip_grad_norm_(self.flat.params, self.max_grad_norm))
 
     def set_ema(self, decay: float | None) -> None:
         """Keep an exponential moving average of the parameters, ``e <- e + (1 - decay) * (p - e)`` in fp32
@@ -87,6 +119,8 @@ class FusedSGD(torch.optim.SGD):
                 loss = closure()
         g = self.param_groups[0]
         self.flat.gather_grads()
+        if self.max_grad_norm is not None:
+            self._clip_grads()
         if self.on_gpu:
             sch = self.lr_schedule
             _native.ops().sgd_flat(self.flat.data, self.flat.grad, self.momentum_flat, float(g["lr"]),

@@ -235,6 +235,38 @@ void sgd_flat(Tensor& p, const Tensor& g, Tensor& buf, double lr, double momentu
                                   lr_table.has_value() ? (int)lr_table->numel() : 0, optpt<int64_t>(lr_pos)));
 }
 
+// [form, grid, partials, one-workgroup max, threads per workgroup] of a clip of n floats (kernels/clip_plan.h)
+std::vector<int64_t> clip_plan(int64_t n) {
+  const csed::ClipPlan p = csed::clip_plan(n);
+  TORCH_CHECK(!p.error, p.error ? p.error : "");
+  return {p.form, p.grid, p.partials, csed::kClipOneWgMax, csed::kClipThreads};
+}
+
+// Global-norm gradient clipping in place, kernels/clip.hip: g is any contiguous float32 tensor or view (4-byte
+// aligned is enough), stats float32 [2] gets (norm before clipping, coefficient), partials is the scratch of the
+// two-launch form (clip_plan(n)[2] floats), unused by the one-workgroup form.
+void clip_grad_norm_(Tensor& g, double max_norm, Tensor& stats, const optional<Tensor>& partials) {
+  dev(g, "g"); dev(stats, "stats");
+  TORCH_CHECK(g.scalar_type() == at::kFloat && g.numel() >= 1, "clip_grad_norm_: g is float32 with at least one element");
+  TORCH_CHECK(stats.scalar_type() == at::kFloat && stats.numel() >= 2 && stats.device() == g.device(),
+              "clip_grad_norm_: stats is float32 [2] on g's device");
+  const csed::ClipPlan p = csed::clip_plan(g.numel());
+  TORCH_CHECK(!p.error, p.error ? p.error : "");
+  if (p.form != 0) {
+    TORCH_CHECK(partials.has_value(), "clip_grad_norm_: ", g.numel(), " elements (more than ", csed::kClipOneWgMax,
+                ") take the two-launch form, which needs partials: float32 [", p.partials, "] (csed::clip_plan)");
+    dev(*partials, "partials");
+    TORCH_CHECK(partials->scalar_type() == at::kFloat && partials->device() == g.device() &&
+                    partials->numel() >= p.partials,
+                "clip_grad_norm_: partials is float32 on g's device with at least ", p.partials, " elements for ",
+                g.numel(), " gradient elements, got ", partials->numel());
+  }
+  const c10::DeviceGuard gd(g.device());
+  CHECK_HIP(csed::launch_clip_grad_norm(g.data_ptr<float>(), g.numel(), (float)max_norm, stats.data_ptr<float>(),
+                                        p.form != 0 ? partials->data_ptr<float>() : nullptr,
+                                        p.form != 0 ? partials->numel() : 0, cur_stream(g)));
+}
+
 // ---------------------------------------------------------------- softmax
 void log_softmax_fwd(const Tensor& x, Tensor& y) {
   dev(x, "x"); dev(y, "y");
@@ -792,7 +824,7 @@ std::vector<int64_t> lenet_geometry(int64_t B, int64_t mfma_dtype, int64_t grid,
 
 // Load the code objects of the kernel translation units named by `mask` on `device` now, from
 // any host thread (bit 0 lenet_fused, 1 lenet_tile, 2 lenet_fused_f32, 3 comm, 4 conv, 5 gemm,
-// 6 elementwise).  The HIP runtime loads a TU's code object lazily at its first launch -- measured
+// 6 elementwise, 7 clip).  The HIP runtime loads a TU's code object lazily at its first launch -- measured
 // on a fresh box: lenet_tile's (the 10k-image validation) 5-60 ms inside epoch 0.  Returns the
 // host milliseconds spent.
 double preload_kernels(int64_t device, int64_t mask) {
@@ -802,9 +834,9 @@ double preload_kernels(int64_t device, int64_t mask) {
   CHECK_HIP(hipSetDevice((int)device));
   hipError_t (*const fns[])() = {csed::preload_lenet_fused, csed::preload_lenet_tile, csed::preload_lenet_f32,
                                  csed::comm::preload_comm, csed::preload_conv, csed::preload_gemm,
-                                 csed::preload_elementwise};
+                                 csed::preload_elementwise, csed::preload_clip};
   hipError_t err = hipSuccess;
-  for (int i = 0; i < 7; ++i)
+  for (int i = 0; i < 8; ++i)
     if ((mask >> i) & 1) {
       const hipError_t e = fns[i]();
       if (err == hipSuccess) err = e;
@@ -1288,6 +1320,8 @@ TORCH_LIBRARY(csed, m) {
         "float max_scale, float alpha) -> ()");
   m.def("augment_stroke(Tensor src, Tensor(a!) dst, Tensor? idx, Tensor? params_in, Tensor(b!)? params_out, int seed, "
         "int epoch, float max_thickness, float erase_p, int erase_lo, int erase_hi) -> ()");
+  m.def("clip_plan(int n) -> int[]", &clip_plan);
+  m.def("clip_grad_norm_(Tensor(a!) g, float max_norm, Tensor(b!) stats, Tensor(c!)? partials) -> ()");
   m.def("sgd_flat(Tensor(a!) p, Tensor g, Tensor(b!) buf, float lr, float momentum, float dampening, "
         "float weight_decay, bool nesterov, float grad_scale, Tensor(c!) step, Tensor(d!) ticket, "
         "Tensor? lr_table=None, Tensor(e!)? lr_pos=None) -> ()");
@@ -1340,6 +1374,7 @@ TORCH_LIBRARY_IMPL(csed, CUDA, m) {
   m.impl("augment_affine", &augment_affine);
   m.impl("augment_elastic", &augment_elastic);
   m.impl("augment_stroke", &augment_stroke);
+  m.impl("clip_grad_norm_", &clip_grad_norm_);
   m.impl("sgd_flat", &sgd_flat);
   m.impl("log_softmax_fwd", &log_softmax_fwd);
   m.impl("log_softmax_bwd", &log_softmax_bwd);

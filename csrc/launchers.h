@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "comm/ipc_allreduce.h"
+#include "kernels/clip_plan.h"   // which form / grid a gradient clip gets
 #include "kernels/lenet_plan.h"  // the dtype codes; which kernel / grid / staging a fused LeNet launch gets
 
 namespace csed {
@@ -62,6 +63,14 @@ hipError_t launch_sgd_flat(float* p, const float* g, float* buf, int64_t n, floa
                            float dampening, float weight_decay, int nesterov, float grad_scale,
                            int64_t* step, int* ticket, hipStream_t s, const float* lr_table = nullptr,
                            int lr_len = 0, int64_t* lr_pos = nullptr);
+
+// Global-norm clip of the flat fp32 gradient g[n], in place (kernels/clip.hip; torch's clip_grad_norm_, 2-norm):
+// norm = sqrt(sum g^2), coef = min(1, max_norm / (norm + 1e-6)), g *= coef; stats[0] = norm, stats[1] = coef.
+// g: any 4-byte aligned address, n >= 1.  clip_plan(n) (kernels/clip_plan.h) picks one launch of one workgroup
+// or, past kClipOneWgMax, two launches over `partials` (>= the plan's `partials` floats; unused and may be null
+// otherwise): hipErrorInvalidValue where it is missing or too small.
+hipError_t launch_clip_grad_norm(float* g, int64_t n, float max_norm, float* stats, float* partials,
+                                 int64_t partials_n, hipStream_t s);
 
 // ------------------------------------------------------------- softmax ----
 // log_softmax over the last dim of x[rows, C] (any float dtype in, fp32 out).
@@ -399,5 +408,6 @@ hipError_t preload_lenet_f32();
 hipError_t preload_conv();
 hipError_t preload_gemm();
 hipError_t preload_elementwise();
+hipError_t preload_clip();
 
 }  // namespace csed
